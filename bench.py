@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — LM iterations / second of the MI355X bundle-adjustment backend.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--dump-outputs DIR] [--full]
 
 A "step" is ONE Levenberg-Marquardt iteration of the reference's global BA (Jacobian sweep when the
 previous step was accepted, Schur complement, dense reduced solve, back-substitution, candidate
@@ -10,6 +10,11 @@ the problem resident in HBM; when a solve terminates inside the timed region the
 reset to the perturbed start (a device-to-device copy) and the next solve begins, so every timed
 step is a real iteration of a real solve. With N > 1 the 3-D points (and their observations) are
 sharded over the ranks and the reduced camera system is all-reduced over RCCL once per iteration.
+
+A plain run sets up, warms up, times the K steps and prints the headline (value, ms_per_step). --full adds what takes
+runs of its own: the kernel table and roofline from a second, event-timed pass over the same K steps, the Jacobian probe,
+one complete solve, the CPU baseline and the short C2 / C5 passes. --dump-outputs DIR writes the parameters and cost the
+timed path holds after its last step as DIR/<name>.npy (float64; inputs are seeded, so two builds compare array for array).
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
 """
@@ -232,6 +237,31 @@ def measure_other_config(name, steps, warmup, device):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, sess, rank, world):
+    """What a caller of the timed path receives after its last step: poses [NI, 6], intrinsics [NC, 9], points [NP, 3] (this
+    rank's shard when N > 1) and cost = [initial, current] (float64). Above the size limit the points are a fixed, seeded
+    sample of rows, listed in points_index."""
+    os.makedirs(out_dir, exist_ok=True)
+    poses, intr, pts = sess.get_params()
+    res = sess.result()
+    arrays = {}
+    if rank == 0:
+        arrays.update(poses=poses, intrinsics=intr, cost=np.array([res["initial_cost"], res["final_cost"]]))
+    suffix = "" if world == 1 else f"_rank{rank}"
+    budget = (DUMP_LIMIT_BYTES - poses.nbytes - intr.nbytes - 1024) // world
+    if pts.nbytes > budget:
+        idx = np.sort(np.random.default_rng(0).choice(len(pts), budget // (pts.itemsize * 3 + 8), replace=False))
+        arrays["points_index" + suffix] = idx.astype(np.float64)
+        pts = pts[idx]
+    arrays["points" + suffix] = pts
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    log(f"[rank {rank}] outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k} {v.shape}" for k, v in arrays.items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -242,7 +272,10 @@ def main():
     ap.add_argument("--problem", default=None, help="replay file (BAProblem.save / the shim's MAVBA_DUMP_DIR) instead of a synthetic config")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=6)
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short C2 / C5 passes of the default single-GPU run (--no-cpu-baseline skips them too: the tuning scripts' form)")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the short C2 / C5 passes of the --full single-GPU run (--no-cpu-baseline skips them too: the tuning scripts' form)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also the event-timed kernel table / roofline pass, the Jacobian probe, one complete "
+                                                        "solve, the CPU baseline and the other configurations (off: the headline only)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -332,7 +365,7 @@ def main():
                      points=int(prob.num_points), observations=int(prob.num_obs))
     ranks = [rank_info]
     ranks_confirmed = 1
-    if world > 1:
+    if world > 1 and args.full:
         ranks = [None] * world
         dist.all_gather_object(ranks, rank_info)
         one = torch.ones(1, dtype=torch.float64, device=f"cuda:{local_rank}")
@@ -368,7 +401,28 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # the same K steps again, from the same start, with HIP events around every kernel: the per-kernel averages of the
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sess, rank, world)
+    value = args.steps / elapsed
+    headline = {
+        "metric": "global-BA LM iterations/sec", "value": round(value, 3), "unit": "iter/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic" if not args.problem else "replay file",
+        "config": {"workload": WORKLOADS[args.config] + ("" if args.scale == 1.0 else f" (scaled x{args.scale})"),
+                   "images": full.num_images, "points": full.num_points, "observations": full.num_obs,
+                   "parallelism": "single GPU" if world == 1 else f"points sharded over {world} ranks, " + exchange +
+                   " of the reduced camera system",
+                   "options": "max_iter 200, ftol 1e-6, gtol 1e-10, ptol 1e-8, Cauchy a=1, refine intrinsics"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        sess.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    # --full: the same K steps again, from the same start, with HIP events around every kernel: the per-kernel averages of the
     # roofline / kernel table (rocprofv3's kernel stats of this command agree with them, profiles/)
     sess.reset()
     sess.set_profiling(True)
@@ -599,7 +653,6 @@ def main():
                     other_configs[name] = measure_other_config(name, k, 6, local_rank)
                 except Exception as e:  # noqa: BLE001
                     other_configs[name] = {"error": str(e)}
-        value = args.steps / elapsed
         # HBM bytes one LM iteration moves (committed counter pass x this run's launch counts) against the algorithmic
         # bytes of ONE Jacobian sweep (48 + 16 + 2 (9 + K) 8 per observation)
         traffic_iter = pmc_traffic_per_iteration(args.config, args.scale, world,
@@ -608,19 +661,11 @@ def main():
             sweep_bytes = algorithmic_work("jacobian_sweep", prob, info)[1]
             traffic_iter.update(algorithmic_sweep_bytes=sweep_bytes, ratio=round(traffic_iter["bytes"] / sweep_bytes, 3))
         out = {
-            "metric": "global-BA LM iterations/sec", "value": round(value, 3), "unit": "iter/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "strong",
+            **headline,
             "ms_per_step_with_event_timers": round(1e3 * elapsed_profiled / args.steps, 4),
             "timing_note": "value / ms_per_step: K steps without any instrumentation; the kernel table, roofline and reduced_solve "
                            "averages come from a second pass over the same K steps with HIP events around every kernel "
                            "(ms_per_step_with_event_timers: each bracket drains the queue for ~10 us; rounds 1-3 quoted that figure as value)",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic" if not args.problem else "replay file",
-            "config": {"workload": WORKLOADS[args.config] + ("" if args.scale == 1.0 else f" (scaled x{args.scale})"),
-                       "images": full.num_images, "points": full.num_points, "observations": full.num_obs,
-                       "parallelism": "single GPU" if world == 1 else f"points sharded over {world} ranks, " + exchange +
-                       " of the reduced camera system",
-                       "options": "max_iter 200, ftol 1e-6, gtol 1e-10, ptol 1e-8, Cauchy a=1, refine intrinsics"},
             "roofline": roofline,
             "reduced_solve": reduced_solve,
             "jacobian_sweep": jacobian_probe,

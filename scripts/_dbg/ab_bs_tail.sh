@@ -5,7 +5,7 @@ set -u
 export TMPDIR=/tmp
 cd "$(dirname "$0")/../.."
 python -m mavmap_amd.build > /dev/null
-bench() { for c in C3 C2; do timeout 300 python bench.py --config $c --steps 60 --warmup 6 --no-cpu-baseline 2>/tmp/b.log | python -c "
+bench() { for c in C3 C2; do timeout 300 python bench.py --full --config $c --steps 60 --warmup 6 --no-cpu-baseline 2>/tmp/b.log | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', d['config']['workload'][:3], d['value'], d['ms_per_step'])"; grep chol_factor /tmp/b.log | head -1; done; }
 bench product; bench product
 cp mavmap_amd/lib/libmavba.so /tmp/libmavba_keep.so

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 cd "$(dirname "$0")/../.."
 L=mavmap_amd/lib
 cp $L/libmavba.so /tmp/libmavba_keep.so
-bench() { for c in $2; do timeout 300 python bench.py --config $c --steps 60 --warmup 6 --no-cpu-baseline 2>/tmp/b.log | python -c "
+bench() { for c in $2; do timeout 300 python bench.py --full --config $c --steps 60 --warmup 6 --no-cpu-baseline 2>/tmp/b.log | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k={x['kernel']:x['avg_ms'] for x in d['kernels']}
 print('$1', d['config']['workload'][:3], d['value'], d['ms_per_step'], 'rows', k.get('schur_fused'), 'sweep', k.get('camera_sweep'), 'backsub', k.get('backsub_points'), 'cost', k.get('cost_only'), 'probe', d['jacobian_sweep'].get('frac'), d['jacobian_sweep'].get('avg_ms'))"; done; }
 for v in base new base new; do

@@ -1,6 +1,6 @@
 """Average cycles per phase of k_schur_fused from a MAVBA_FUSED_TRACE file (debug harness).
 
-  MAVBA_FUSED_TRACE=/tmp/f.txt python bench.py --steps 8 --warmup 2 --no-cpu-baseline; python scripts/_dbg/fused_trace.py /tmp/f.txt
+  MAVBA_FUSED_TRACE=/tmp/f.txt python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline; python scripts/_dbg/fused_trace.py /tmp/f.txt
 """
 import sys
 import numpy as np

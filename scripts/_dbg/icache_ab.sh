@@ -8,7 +8,7 @@ R=$PWD
 python -m mavmap_amd.build > /dev/null
 run() {
   d=$R/gpurun_out/icache_$1; rm -rf $d
-  (cd /tmp && timeout 300 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE --kernel-trace --output-format csv -d $d -o pmc -- python $R/bench.py --steps 20 --warmup 4 --no-cpu-baseline > /dev/null 2>&1)
+  (cd /tmp && timeout 300 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE --kernel-trace --output-format csv -d $d -o pmc -- python $R/bench.py --full --steps 20 --warmup 4 --no-cpu-baseline > /dev/null 2>&1)
   python - "$d" "$1" <<'PY'
 import csv, glob, sys, collections
 d, tag = sys.argv[1], sys.argv[2]
@@ -29,8 +29,8 @@ cp mavmap_amd/lib/libmavba.so /tmp/libmavba_keep.so
 objs=$(ls mavmap_amd/lib/obj/*.o | grep -v dense_chol)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o mavmap_amd/lib/libmavba.so $objs /tmp/dense_chol_la.o
 run tile_la
-for c in C3 C2; do timeout 300 python bench.py --config $c --steps 60 --warmup 6 --no-cpu-baseline 2>/tmp/b.log | python -c "
+for c in C3 C2; do timeout 300 python bench.py --full --config $c --steps 60 --warmup 6 --no-cpu-baseline 2>/tmp/b.log | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('tile_la', d['config']['workload'][:3], d['value'], d['ms_per_step'])"; grep chol_factor /tmp/b.log | head -1; done
 cp /tmp/libmavba_keep.so mavmap_amd/lib/libmavba.so
-for c in C3 C2; do timeout 300 python bench.py --config $c --steps 60 --warmup 6 --no-cpu-baseline 2>/tmp/b.log | python -c "
+for c in C3 C2; do timeout 300 python bench.py --full --config $c --steps 60 --warmup 6 --no-cpu-baseline 2>/tmp/b.log | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('product', d['config']['workload'][:3], d['value'], d['ms_per_step'])"; grep chol_factor /tmp/b.log | head -1; done

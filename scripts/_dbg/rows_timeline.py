@@ -1,7 +1,7 @@
 """Time line of one k_schur_rows launch from a MAVBA_ROWS_TRACE file (debug harness, round 6): per cluster the ticks of
 its tables (entry -> first batch), its batches and its emit (differences of stamps inside one work-group).
 
-  MAVBA_ROWS_TRACE=/tmp/r.txt python bench.py --steps 8 --warmup 2 --no-cpu-baseline; python scripts/_dbg/rows_timeline.py /tmp/r.txt
+  MAVBA_ROWS_TRACE=/tmp/r.txt python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline; python scripts/_dbg/rows_timeline.py /tmp/r.txt
 """
 import sys
 import collections

@@ -1,7 +1,7 @@
 """Average cycles per phase of k_schur_rows from a MAVBA_ROWS_TRACE file (debug harness; second batch of the clusters of one row class,
 default class 1 = 96 rows).
 
-  MAVBA_ROWS_TRACE=/tmp/r.txt python bench.py --steps 8 --warmup 2 --no-cpu-baseline; python scripts/_dbg/rows_trace.py /tmp/r.txt
+  MAVBA_ROWS_TRACE=/tmp/r.txt python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline; python scripts/_dbg/rows_trace.py /tmp/r.txt
 """
 import sys
 import numpy as np

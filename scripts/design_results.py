@@ -3,7 +3,7 @@ import json
 import sys
 
 d = json.load(open(sys.argv[1]))
-print(f"`python bench.py` ({d['config']['workload']}, 1 GPU, {d['steps']} timed LM iterations):")
+print(f"`python bench.py --full` ({d['config']['workload']}, 1 GPU, {d['steps']} timed LM iterations):")
 print(f"**{d['value']} LM iterations/s** ({d['ms_per_step']} ms per iteration); one complete solve: "
       f"{d['solve']['iterations']} iterations, {d['solve']['termination']}, RMSE {d['solve']['rmse_px']} px, "
       f"{d['solve']['solve_seconds']} s solve + {d['solve']['setup_seconds']} s host set-up.")

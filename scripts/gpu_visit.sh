@@ -9,7 +9,7 @@ if [ -n "$PYT" ]; then
   timeout 1500 python -m pytest $PYT -q --tb=short -p no:cacheprovider --timeout 600 > $OUT/pytest.log 2>&1; echo "pytest rc $?"; tail -25 $OUT/pytest.log
 fi
 for c in $CFGS; do
-  MAVBA_CLUSTER_STATS=1 timeout 400 python bench.py --config $c --steps 60 --warmup 6 --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.log
+  MAVBA_CLUSTER_STATS=1 timeout 400 python bench.py --full --config $c --steps 60 --warmup 6 --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.log
   grep -E "cluster stats" $OUT/bench_$c.log | sort | uniq | head -4
   grep -E "^\| .(schur_fused|chol_factor|chol_backsolve|backsub_points|camera_sweep|schur_finalize|point_front)" $OUT/bench_$c.log | head -8
   python -c "

@@ -10,7 +10,7 @@ mkdir -p $OUT
 nproc > $OUT/nproc.txt
 # kernel trace + stats (own run)
 rm -rf $OUT/prof
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python $R/bench.py --steps 60 --warmup 6 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof_bench.log); echo "rocprof rc $?"
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python $R/bench.py --full --steps 60 --warmup 6 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof_bench.log); echo "rocprof rc $?"
 find $OUT/prof -name "*kernel_stats*.csv" -exec cp {} $OUT/bench_C3_kernel_stats.csv \;
 find $OUT/prof -name "*kernel_trace*.csv" -size +8M -delete
 # PMC passes (each its own run, kernel-trace only)
@@ -25,6 +25,6 @@ rm -rf $R/gpurun_out/pmc $OUT/prof
 cp $OUT/pmc_traffic_C3.json $R/profiles/${TAG}_pmc_traffic_C3.json
 cp $OUT/pmc_mfma_C3.json $R/profiles/${TAG}_pmc_mfma_C3.json
 for C in C3 C2 C5; do
-  timeout 600 python bench.py --config $C --steps 60 --warmup 6 > $OUT/bench_$C.json 2> $OUT/bench_$C.log; echo "bench $C rc $?"
+  timeout 600 python bench.py --full --config $C --steps 60 --warmup 6 > $OUT/bench_$C.json 2> $OUT/bench_$C.log; echo "bench $C rc $?"
 done
 ls -la $OUT

@@ -300,7 +300,7 @@ def test_the_drivers_multi_gpu_bench_command_with_two_ranks_on_one_gpu(mavba):
     two ranks SHARING this box's GPU: MAVBA_DIST_BACKEND=gloo (RCCL refuses two ranks on one device), so the exchange goes
     through the torch.distributed hook. What it pins before an 8-GPU node exists: argument parsing and the rank / world
     environment, the sharding of the configuration, the barrier + max-over-ranks timing, ONE JSON line from rank 0 with the
-    contract's keys, n_gpus, "scaling": "strong" and the Amdahl bound of the replicated solve."""
+    contract's keys, n_gpus, "scaling": "strong" and (--full) the Amdahl bound of the replicated solve."""
     import json
     import os
     import socket
@@ -312,7 +312,7 @@ def test_the_drivers_multi_gpu_bench_command_with_two_ranks_on_one_gpu(mavba):
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2", "--config", "C2", "--scale", "0.2",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     env = dict(os.environ, MAVBA_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

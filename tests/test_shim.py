@@ -19,22 +19,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
 
 
-REFERENCE_SRC = "/root/reference/src"   # build container only (never present on the GPU box)
+# The shim linked with the reference's own FeatureManager is compiled by build() (`make -C oracle ref`), only where the
+# reference sources are present; like everything compiled from them it lives under oracle/_ref (git-ignored).
+REFERENCE_FM_SHIM = os.path.join(ROOT, "oracle", "_ref", "_shim_mock_reffm.so")
+REFERENCE_FM_SHIM_DEPS = [os.path.join(ROOT, *f) for f in (("tests", "shim", "shim_driver.cpp"), ("tests", "shim", "mock_mavba.cpp"),
+                                                          ("shim", "base3d", "bundle_adjustment.cc"),
+                                                          ("shim", "base3d", "bundle_adjustment.h"), ("include", "mavba.h"))]
 
 
-def _build(real, reference_fm=False):
-    """reference_fm: compile against the REFERENCE's own src/fm/feature_management.{h,cc} (the real FeatureManager class,
-    its sources used where they lie, only the Eigen vector types come from the test double) instead of the 26-line
-    FeatureManager double in tests/stubs."""
+def _build(real):
     out = os.path.join(ROOT, "tests", "shim", "_shim_real.so" if real else "_shim_mock.so")
-    if reference_fm:  # anything compiled from the reference's sources lives under oracle/_ref (git-ignored)
-        os.makedirs(os.path.join(ROOT, "oracle", "_ref"), exist_ok=True)
-        out = os.path.join(ROOT, "oracle", "_ref", "_shim_mock_reffm.so")
     srcs = [os.path.join(ROOT, "tests", "shim", "shim_driver.cpp"), os.path.join(ROOT, "shim", "base3d", "bundle_adjustment.cc")]
     inc = ["-I" + os.path.join(ROOT, "shim")]
-    if reference_fm:  # shim/ first (its base3d/bundle_adjustment.h replaces the reference's), then the reference tree for fm/
-        inc.append("-I" + REFERENCE_SRC)
-        srcs.append(os.path.join(REFERENCE_SRC, "fm", "feature_management.cc"))
     cmd = ["g++", "-std=c++11", "-O1", "-pthread", "-fPIC", "-shared"] + inc + ["-I" + os.path.join(ROOT, "tests", "stubs"),
            "-I" + os.path.join(ROOT, "include")] + srcs
     if real:
@@ -46,8 +42,7 @@ def _build(real, reference_fm=False):
     return C.CDLL(out)
 
 
-def _mock_library(reference_fm):
-    L = _build(real=False, reference_fm=reference_fm)
+def _mock_library(L):
     for name, rt in (("mock_poses", dp), ("mock_intr", dp), ("mock_points", dp), ("mock_uv", dp), ("mock_prior_rvec", dp),
                      ("mock_pose_const", bp), ("mock_intr_const", bp), ("mock_point_const", bp),
                      ("mock_image_camera", ip), ("mock_camera_model", ip), ("mock_obs_image", ip),
@@ -61,15 +56,18 @@ def _mock_library(reference_fm):
 
 @pytest.fixture(scope="module")
 def mock():
-    return _mock_library(False)
+    return _mock_library(_build(real=False))
 
 
 @pytest.fixture(scope="module")
 def mock_reference_fm():
-    """The shim compiled against the reference's real FeatureManager (header AND feature_management.cc)."""
-    if not os.path.isdir(os.path.join(REFERENCE_SRC, "fm")):
-        pytest.skip("needs /root/reference (build container only)")
-    return _mock_library(True)
+    """The shim compiled against the reference's real FeatureManager (header AND feature_management.cc), its sources used
+    where they lie, only the Eigen vector types from the test double in tests/stubs: built by build(), see above."""
+    if not os.path.exists(REFERENCE_FM_SHIM):
+        pytest.skip("oracle/_ref/_shim_mock_reffm.so not built: build() compiles it only where the reference sources are present")
+    stale = [d for d in REFERENCE_FM_SHIM_DEPS if os.path.getmtime(d) > os.path.getmtime(REFERENCE_FM_SHIM)]
+    assert not stale, f"oracle/_ref/_shim_mock_reffm.so is older than {stale}: run build() again"
+    return _mock_library(C.CDLL(REFERENCE_FM_SHIM))
 
 
 class Scene:
