@@ -14,7 +14,7 @@ LIBDIR = os.path.join(ROOT, "lib")
 LIB = os.path.join(LIBDIR, "libmavba.so")
 OBJDIR = os.path.join(LIBDIR, "obj")
 SOURCES = ["kernels.hip", "schur_rows.hip", "dense_chol.hip", "pose_refine.hip", "host_util.hip", "session_build.hip", "session_lm.hip", "scene.hip", "multi_gpu.hip", "device_setup.hip", "api.hip"]
-HEADERS = ["ba_math.h", "dev_reduce.h", "internal.h", "session.h", "lm_decide.h", "lm_bodies.h", "sweep_body.h", os.path.join("..", "..", "include", "mavba.h")]
+HEADERS = ["ba_math.h", "dev_reduce.h", "internal.h", "session.h", "lm_decide.h", "lm_bodies.h", "sweep_body.h", "launch_dispatch.h", os.path.join("..", "..", "include", "mavba.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wall",
          "-Wno-unused-result"]
 # Per-file additions. dense_chol.hip: matrix instructions with their accumulators in ordinary vector registers - the
@@ -31,6 +31,17 @@ def _hipcc():
 
 
 STAMP = os.path.join(LIBDIR, "build_stamp.json")
+
+
+def files_digest(paths):
+    """sha256 (hex) over the names (without directories) and contents of `paths`: what the stamp of a build product outside
+    this module records (content, not mtimes, as below)."""
+    import hashlib
+    h = hashlib.sha256()
+    for p in paths:
+        with open(p, "rb") as fh:
+            h.update(os.path.basename(p).encode() + b"\0" + fh.read())
+    return h.hexdigest()
 
 
 def source_digest():

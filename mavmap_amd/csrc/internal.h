@@ -49,27 +49,20 @@ void launch_partial_reduce(hipStream_t st, int num_tasks, const PartialReduce* t
                            double* part_ii);  // term range; slot = index of the partial it writes
 
 // Point clusters of the Schur complement (k_schur_clusters): a run of consecutive points [p0, p1) whose
-// images fit a local list of kClImages and whose shared cameras fit kClCams. The cluster's contribution to
+// images fit a local list of kClImagesMax and whose shared cameras fit kClCamsMax. The cluster's contribution to
 // EVERY block among its images / cameras is one symmetric product E E^T of its stacked entry matrix
-//   rows  6*la + r        : U_a (6 x 3) of the observation in local image la      (la < kClImages)
-//   rows  96 + 9*lc + r   : Uk  (9 x 3) of the point's entry for local camera lc  (lc < kClCams)
+//   rows  6*la + r        : U_a (6 x 3) of the observation in local image la      (la < kClImagesMax)
+//   rows  96 + 9*lc + r   : Uk  (9 x 3) of the point's entry for local camera lc  (lc < kClCamsMax)
 //   row   123             : h^T of the point                                       (gives e_a / ek)
 //   cols  3*point + t
 // computed on the FP64 matrix cores from LDS; each block that is present in the cluster then leaves as
 // ONE partial (slot table) instead of one gathered term per (point, pair).
-// Two shapes: 16 images x 3 cameras (128 rows, 36 lower 16x16 tiles) and 12 images x 2 cameras (96 rows, 21 tiles:
-// 42 % fewer matrix instructions when the tracks are short and at most two cameras are refined).
-struct ClusterShape {
-  int images, cams;
-  int cam_row0() const { return 6 * images; }
-  int hrow() const { return 6 * images + 9 * cams; }
-  int rows() const { return (hrow() + 1 + 15) / 16 * 16; }
-  int tab_pp() const { return 0; }
-  int tab_ip() const { return images * (images + 1) / 2; }
-  int tab_ii() const { return tab_ip() + cams * images; }
-  int tab() const { return tab_ii() + cams * (cams + 1) / 2; }
-};
+// One shape: 16 images x 3 cameras (128 rows, 36 lower 16x16 tiles). Slot table of a cluster: pose x pose pairs (lower
+// triangle) | intrinsics x pose | intrinsics x intrinsics pairs.
 constexpr int kClImagesMax = 16, kClCamsMax = 3;
+constexpr int kClCamRow0 = 6 * kClImagesMax, kClHRow = kClCamRow0 + 9 * kClCamsMax, kClRows = (kClHRow + 16) / 16 * 16;
+constexpr int kClTabPP = 0, kClTabIP = kClImagesMax * (kClImagesMax + 1) / 2, kClTabII = kClTabIP + kClCamsMax * kClImagesMax,
+              kClTab = kClTabII + kClCamsMax * (kClCamsMax + 1) / 2;
 constexpr int kClBatch = 32;                     // points per LDS batch -> K = 96 columns (16 -> two work-groups per CU, measured slower)
 constexpr int kTailObs = 16;                     // a point with more observations than a cluster has images sorts into the tail of the point order
 constexpr int kClMaxBatches = 64;                // a cluster spans at most kClMaxBatches * kClBatch consecutive points
@@ -90,7 +83,7 @@ inline unsigned image_set_mix(unsigned x) {
 // has rows 6 * slot + e for its `ni` image slots, then the parameters of its `nc` camera slots (4 / 8 / 9 rows each), then the
 // h row; the cluster's ROW CLASS (16-row blocks NT of the matrix) selects the batch loop: 80 rows hold 11 images + a PINHOLE and
 // an OPENCV camera + h (15 tiles), 96 rows 13 images (21 tiles), 128 rows the general 16 x 3 list (36 tiles). Slot tables and
-// image / camera lists keep the 16 x 3 layout of ClusterShape{16, 3}: a cluster of k_schur_rows is also a valid cluster of
+// image / camera lists keep the 16 x 3 layout of k_schur_clusters: a cluster of k_schur_rows is also a valid cluster of
 // k_schur_clusters.
 constexpr int kRowsBatch = 16;
 constexpr int kRowsMaxPoints = 256;
@@ -221,7 +214,7 @@ struct FrontArgs {
   double* Cu; double* gu; double* Gi; double* h;   // per-point planes, stride NPs
   double* Epose; double* Eintr;                     // entry records (kPoseRec / kIntrRec doubles)
   double* fail;
-  long long* trace;  // MAVBA_FRONT_TRACE (debugging): s_memtime stamps per work-group, else null
+  long long* trace;  // MAVBA_ROWS_TRACE (debugging, k_schur_rows): s_memtime stamps per wave, else null
   LmSpec spec;       // speculative evaluation: run only if the pending candidate is accepted, with the radius it leaves (`radius` is ignored then)
 };
 int point_front_grid(int num_tiles);
@@ -239,10 +232,6 @@ struct CamSweepArgs {
   LmSpec spec;      // speculative evaluation (see FrontArgs)
 };
 void launch_camera_sweep(hipStream_t st, const CamSweepArgs& a, int kmax, bool any_intr_free);
-void launch_camera_reduce(hipStream_t st, int NI, int NC, const int* img_chunk_start,
-                          const double* partial, const int* prior_start, const double* prior_res,
-                          const double* prior_jac, const int* cam_img_start, const int* cam_imgs,
-                          double* img_rec, double* cam_rec, double* img_intr_tmp, bool with_cams = true, const LmSpec& spec = lm_spec_off(), const PartialRide& ride = PartialRide());
 void launch_rot_prior(hipStream_t st, int n, const int* prior_img, const double* prior_R0, double w,
                       const double* poses, double* res, double* jac, double* cost_partial, const LmSpec& spec = lm_spec_off());
 
@@ -252,17 +241,7 @@ void launch_scales(hipStream_t st, int NI, int NC, int NP, int NPs, int jacobi,
                    const double* Cu, double* scale_cam, double* scale_pt);
 
 constexpr int kStateNormsCamBlocks = 64;  // partial[] holds 2 x (512 + this) values
-void launch_state_norms(hipStream_t st, int NI, int NC, int NP, int NPs, bool cam_part,
-                        const unsigned char* pose_free, const unsigned char* intr_free,
-                        const unsigned char* pt_free, const double* poses, const double* intr,
-                        const double* points, const double* img_rec, const double* cam_rec,
-                        const double* gu, double* partial /*[grid][2]*/, int* grid_out, const LmSpec& spec = lm_spec_off());
 
-
-void launch_entries_pose(hipStream_t st, int N, int Nstride, int NPs, const int* obs_img,
-                         const int* obs_pt, const unsigned char* pt_free, const double* Jc,
-                         const double* Jp, const double* scale_cam, const double* scale_pt,
-                         double* Gi, double* h, double* Epose);
 void launch_factor_entries_pose(hipStream_t st, int N, int Nstride, int NPs, const int* obs_img, const int* obs_pt,
                                 const unsigned char* pt_free, const double* Jc, const double* Jp, const double* scale_cam,
                                 const double* scale_pt, double* Gi, double* h, double* Epose, const int* pt_start,
@@ -274,7 +253,11 @@ void launch_entries_intr(hipStream_t st, int Q, int NI, int NPs, const int* q_pt
 void launch_schur_chunks(hipStream_t st, int kind, int num_chunks, const SchurChunk* chunks,
                          const int2* terms, const double* Epose, const double* Eintr,
                          double* partial);
-int schur_partial_stride(int kind);
+// doubles per block partial: the block's elements + (diagonal kinds) its right-hand-side part
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+constexpr int schur_partial_stride(int kind) { return kind == BLK_PP ? 42 : kind == BLK_IP ? 54 : 90; }
 // front end + cluster kernel in one launch (problems whose every observed point is clustered; cluster shape 16 x 3):
 // a.sw.cost_partial gets one partial per cluster (k_schur_rows, schur_rows.hip; its round-3 predecessor k_schur_fused lives in
 // scripts/_dbg/pruned_r06.patch)
@@ -291,7 +274,7 @@ void rows_emit_map(int ni, int nc, int flags, std::vector<unsigned>& pass0, std:
 constexpr unsigned long long kRowsLanesIdentity = 0xFEDCBA9876543210ull;
 // obs_meta / q_meta: per observation / intrinsics entry, local index << 8 | (point - cluster.p0) % kClBatch,
 // 0xFFFF for records that are not part of a cluster.
-void launch_schur_clusters(hipStream_t st, ClusterShape shape, int num_clusters, const SchurCluster* clusters, const int* tab,
+void launch_schur_clusters(hipStream_t st, int num_clusters, const SchurCluster* clusters, const int* tab,
                            const int* pt_start, const int* q_start, const unsigned short* obs_meta,
                            const unsigned short* q_meta, const unsigned char* pt_clustered, const double* Epose,
                            const double* Eintr, const double* h, int NPs, double* part_pp, double* part_ip,
@@ -324,17 +307,15 @@ void launch_backsub_points_jvp(hipStream_t st, int NP, int NPs, int NI, double r
                                const double* gu, const double* scale_pt, double* cand_points, double* delta_points,
                                double* partial /*[grid][3]*/, const double* cand_camrec = nullptr, const double* cand_intr = nullptr,
                                double* cost_partial = nullptr);
+// Camera columns: step = -y, delta = s * step, candidate parameters and (cand_camrec != null) their camera records.
+// mavba_session::cam_update_args fills one per radius; the reduced solve of a small system applies it in its own launch.
+struct CamUpdateArgs {
+  int NI, NC, cam_part; double radius, dmin, dmax;
+  const double* scale_cam; const double* img_rec; const double* cam_rec; const double* poses; const double* intr;
+  double* cand_poses; double* cand_intr; double* delta_cam; double* partial3 /*[groups][3]*/; double* cand_camrec;
+};
 int update_cameras_groups(int NI);  // triples launch_update_cameras writes to partial3
-void launch_update_cameras(hipStream_t st, int NI, int NC, bool cam_part, double radius, double dmin,
-                           double dmax, const double* y, const double* scale_cam,
-                           const double* img_rec, const double* cam_rec, const double* poses,
-                           const double* intr, double* cand_poses, double* cand_intr,
-                           double* delta_cam, double* partial3 /*[groups][3]*/, double* cand_camrec /* null: no camera records */);
-
-// Deterministic reductions of per-block partials: out[c] = op_c(partial[:, c]).
-// op bit c of `max_mask` set -> max, else sum. Adds into out if accumulate.
-void launch_reduce_cols(hipStream_t st, const double* partial, int rows, int cols, int stride,
-                        unsigned max_mask, double* out, bool accumulate);
+void launch_update_cameras(hipStream_t st, const CamUpdateArgs& u, const double* y);
 
 struct ReduceTask { const double* src; int rows, stride, is_max; const double* src2; int rows2; double* out; };
 struct ReduceTasks { ReduceTask t[6]; };
@@ -346,10 +327,11 @@ void launch_lm_snapshot(hipStream_t st, const LmSpec& spec, double* dec, double*
 void launch_lm_decide_cases(hipStream_t st, int n, const double* in, double* out);  // test entry
 // k_reduce_tasks + k_lm_snapshot in one work-group (the n reductions one after the other, then the decision)
 void launch_lm_tail(hipStream_t st, const ReduceTasks& tasks, int n, const LmSpec& spec, double* dec, double* host_pub, double seq, double* fail_slots);
-// The tail of an evaluation in one work-group - k_camera_reduce_img, k_camera_reduce_cam, k_state_norms, k_reduce_tasks - for
-// problems whose images, cameras and points one work-group walks in a few microseconds (a local window). Same sums, same order.
-void state_norms_grid(int NI, int NC, int NP, int* gp, int* gc);  // point groups + camera groups of launch_state_norms
-struct EvalSmallArgs {
+// The tail of an evaluation: per-image sums (k_camera_reduce_img), per-camera sums (k_camera_reduce_cam), norms
+// (k_state_norms: gp point groups + gc camera groups, state_norms_grid) and the three scalar reductions (k_reduce_tasks).
+// mavba_session::eval_tail_args fills one of these per evaluation; every route below starts from it. Same sums, same order.
+void state_norms_grid(int NI, int NC, int NP, int* gp, int* gc);
+struct EvalTailArgs {
   int NI, NC, NP, NPs, with_cams, cam_part, gp, gc, num_tasks;
   int first_group = 0;  // k_eval_tail: the norm groups below this one (the points') were done by k_eval_head
   const int* img_chunk_start; const double* cam_partial; const int* prior_start; const double* prior_res; const double* prior_jac;
@@ -357,13 +339,17 @@ struct EvalSmallArgs {
   const unsigned char* pose_free; const unsigned char* intr_free; const unsigned char* pt_free;
   const double* poses; const double* intr; const double* points; const double* gu; double* norm_partial;
   ReduceTasks T; LmSpec spec;
-  PartialRide ride;  // k_eval_head only
+  PartialRide ride;  // k_eval_head / k_camera_reduce_img only
 };
-void launch_eval_small(hipStream_t st, const EvalSmallArgs& a);
-// the same for problems of any size, as TWO launches (round 5): per-image sums and the points' norm groups side by side
-// in one grid, then one work-group for the per-camera sums, the cameras' norm groups and the three reductions
-void launch_eval_head_tail(hipStream_t st, const EvalSmallArgs& a);
-bool eval_head_tail_fits(int gc);
+// four launches (any size, any number of ranks: the camera sums are all-reduced between the first and the second) ...
+void launch_camera_reduce(hipStream_t st, const EvalTailArgs& a);  // k_camera_reduce_img (+ a.ride), k_camera_reduce_cam if a.with_cams
+void launch_state_norms(hipStream_t st, const EvalTailArgs& a);    // a.gp + a.gc rows of a.norm_partial
+// (then launch_reduce_tasks(st, a.T, a.num_tasks, a.spec))
+// ... ONE work-group, for problems whose images, cameras and points it walks in a few microseconds (a local window) ...
+void launch_eval_small(hipStream_t st, const EvalTailArgs& a);
+// ... or TWO launches (round 5): per-image sums and the points' norm groups side by side in one grid, then one work-group
+// for the per-camera sums, the cameras' norm groups and the three reductions
+void launch_eval_head_tail(hipStream_t st, const EvalTailArgs& a);
 
 void launch_points_to_caller(hipStream_t st, int NP, int width, const int* orig, const double* in, double* out);
 void launch_point_errors(hipStream_t st, int NP, const int* pt_start, const double* rnorm,
@@ -496,14 +482,9 @@ struct CholStructure {
 };
 // y_scatter (may be null): y_nat[y_scatter[t]] = y[t] for every t with y_scatter[t] >= 0 (the solution in
 // the caller's variable order when the matrix was assembled in a permuted order).
-// upd (may be null): the camera update that follows the solve in the LM loop (launch_update_cameras' arguments; y = y_nat).
+// upd (may be null): the camera update that follows the solve in the LM loop (CamUpdateArgs above; y = y_nat).
 // A system of one or two tile columns is solved by ONE work-group, which then applies the update as well: the return value
 // says whether it did (the caller skips its own launch).
-struct CamUpdateArgs {
-  int NI, NC, cam_part; double radius, dmin, dmax;
-  const double* scale_cam; const double* img_rec; const double* cam_rec; const double* poses; const double* intr;
-  double* cand_poses; double* cand_intr; double* delta_cam; double* partial3; double* cand_camrec;
-};
 bool dense_spd_solve_is_small(int n_pad, const CholStructure& cs);  // the one-work-group path will be taken
 // M, L: tile stores of cs (cs.store_doubles() doubles each).
 bool dense_spd_solve_device(hipStream_t st, double* M, int n_pad, double* y, double* fail,

@@ -18,6 +18,7 @@
 #include "lm_decide.h"
 #include "lm_bodies.h"
 #include "sweep_body.h"
+#include "launch_dispatch.h"
 
 namespace mavba {
 
@@ -209,25 +210,25 @@ void launch_jacobian_sweep(hipStream_t st, const SweepArgs& a) {
   const size_t lds = camera_lds_bytes(a.NI, a.NC);
   const bool use_lds = lds <= cam_lds_limit();
   const size_t shm = use_lds ? lds : 64;
-#define MAVBA_SWEEP(K)                                                                                           \
-  if (a.pt_active) {                                                                                             \
-    if (use_lds) hipLaunchKernelGGL((k_jacobian_sweep<K, true, true>), dim3(grid), dim3(256), shm, st, a);       \
-    else hipLaunchKernelGGL((k_jacobian_sweep<K, false, true>), dim3(grid), dim3(256), shm, st, a);              \
-  } else if (use_lds) hipLaunchKernelGGL((k_jacobian_sweep<K, true, false>), dim3(grid), dim3(256), shm, st, a); \
-  else hipLaunchKernelGGL((k_jacobian_sweep<K, false, false>), dim3(grid), dim3(256), shm, st, a);
-  if (a.KMAX <= 4) { MAVBA_SWEEP(4) } else if (a.KMAX <= 8) { MAVBA_SWEEP(8) } else { MAVBA_SWEEP(9) }
-#undef MAVBA_SWEEP
+  with_width(a.KMAX, [&](auto k) {
+    with_bool(use_lds, [&](auto lds_cam) {
+      with_bool(a.pt_active != nullptr, [&](auto mask) {
+        hipLaunchKernelGGL((k_jacobian_sweep<decltype(k)::value, decltype(lds_cam)::value, decltype(mask)::value>), dim3(grid), dim3(256), shm, st, a);
+      });
+    });
+  });
 }
 void launch_cost_only(hipStream_t st, const SweepArgs& a) {
   if (a.N <= 0) return;
   const int grid = jacobian_sweep_grid(a.N);  // same partial count as the sweep
   const size_t lds = camera_lds_bytes(a.NI, a.NC);
   const bool use_lds = lds <= cam_lds_limit();
-  if (a.pt_active) {
-    if (use_lds) hipLaunchKernelGGL((k_cost_only<true, true>), dim3(grid), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((k_cost_only<false, true>), dim3(grid), dim3(256), 64, st, a);
-  } else if (use_lds) hipLaunchKernelGGL((k_cost_only<true, false>), dim3(grid), dim3(256), lds, st, a);
-  else hipLaunchKernelGGL((k_cost_only<false, false>), dim3(grid), dim3(256), 64, st, a);
+  const size_t shm = use_lds ? lds : 64;
+  with_bool(use_lds, [&](auto lds_cam) {
+    with_bool(a.pt_active != nullptr, [&](auto mask) {
+      hipLaunchKernelGGL((k_cost_only<decltype(lds_cam)::value, decltype(mask)::value>), dim3(grid), dim3(256), shm, st, a);
+    });
+  });
 }
 void launch_raw_residual_norm(hipStream_t st, const SweepArgs& a, double* out_norm) {
   if (a.N <= 0) return;
@@ -372,10 +373,10 @@ void launch_point_reduce(hipStream_t st, int NP, int NPs, int Nstride, int KMAX,
                          double* Wk) {
   if (NP <= 0) return;
   const dim3 g((NP + 15) / 16), b(256);
-#define MAVBA_PR(K) hipLaunchKernelGGL((k_point_reduce<K>), g, b, 0, st, NP, NPs, Nstride, pt_start, q_start, q_cam, \
-                                       obs_img, img_cam, R, Jp, Jk, Cu, gu, Wk)
-  if (KMAX <= 4) MAVBA_PR(4); else if (KMAX <= 8) MAVBA_PR(8); else MAVBA_PR(9);
-#undef MAVBA_PR
+  with_width(KMAX, [&](auto k) {
+    hipLaunchKernelGGL((k_point_reduce<decltype(k)::value>), g, b, 0, st, NP, NPs, Nstride, pt_start, q_start, q_cam, obs_img, img_cam, R, Jp,
+                       Jk, Cu, gu, Wk);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -407,13 +408,10 @@ struct FrontShape {
 };
 }  // namespace
 
-template <int KMAX, bool ENTRIES, bool MASK, bool TRACE = false>
+template <int KMAX, bool ENTRIES, bool MASK>
 __global__ void __launch_bounds__(256, 2) k_point_front(FrontArgs a) {  // two work-groups per CU (LDS and registers)
   using SH = FrontShape<KMAX>;
   if (!lm_spec_go(a.spec, &a.radius)) return;  // (speculative evaluation: only behind an accepted step, with the radius it leaves)
-  long long stamp[TRACE ? 12 : 1];
-  int nstamp = 0;
-  auto mark = [&]() { if constexpr (TRACE) { if (nstamp < 12) stamp[nstamp++] = (long long)__builtin_amdgcn_s_memtime(); } };
   extern __shared__ __attribute__((aligned(16))) double fr_smem[];
   double* s_park = fr_smem;                         // [NR][kFrPitch] the window's products of this round
   double* s_q = fr_smem + SH::PARK;                 // [kFrontQ][K3]  Wk sums
@@ -454,8 +452,6 @@ __global__ void __launch_bounds__(256, 2) k_point_front(FrontArgs a) {  // two w
   };
   if (t_begin < t_end) request_tile(t_begin);
   for (int tile = t_begin; tile < t_end; ++tile) {
-    nstamp = 0;
-    mark();  // 0: top of the tile (the trace keeps the work-group's LAST tile: steady state, prefetched)
     const FrontTile T = Tn;
     const int np = T.p1 - T.p0;
     const int o0 = T.o0, o1 = T.o1;
@@ -500,7 +496,6 @@ __global__ void __launch_bounds__(256, 2) k_point_front(FrontArgs a) {  // two w
       for (int e = 0; e < 18; ++e) jk[e] = wgt * Jk[e];
       return half_rho;
     };
-    mark();  // 1: first loads out, tile bookkeeping written
     // ---- phase 1: per-point sums ----
     for (int base = o0; base < o1; base += kFrontObs) {
       const int o = base + tid;
@@ -521,7 +516,6 @@ __global__ void __launch_bounds__(256, 2) k_point_front(FrontArgs a) {  // two w
 #pragma unroll
           for (int t = 0; t < 3; ++t) prod[9 + 3 * k + t] = jk[k] * jp[t] + jk[9 + k] * jp[3 + t];
       }
-      mark();  // 2: Jacobian + products in registers
       auto round = [&](auto rc) {
         constexpr int R = decltype(rc)::value;
         constexpr int lo = R * SH::NR, hi = (lo + SH::NR < SH::NROWS) ? lo + SH::NR : SH::NROWS;
@@ -572,9 +566,7 @@ __global__ void __launch_bounds__(256, 2) k_point_front(FrontArgs a) {  // two w
         }
       };
       round(std::integral_constant<int, 0>{});
-      mark();  // 3: round 0
       if constexpr (SH::ROUNDS > 1) round(std::integral_constant<int, 1>{});
-      mark();  // 4: round 1
       lds_barrier();  // sums complete; the park buffer is free for the next window
     }
     if (tile + 1 < t_end) request_tile(tile + 1);  // (arrives under the rest of this tile)
@@ -623,7 +615,6 @@ __global__ void __launch_bounds__(256, 2) k_point_front(FrontArgs a) {  // two w
     }
     if constexpr (ENTRIES) {
       lds_barrier();
-      mark();  // 5: owner lanes done
       // ---- intrinsics entry records: Uk = (s_k Wk s_p) Gi^T (9 x 3), ek = Uk h; one lane per (record, parameter) ----
       if constexpr (KMAX > 0) {
         for (int it = tid; it < nq * 9; it += 256) {
@@ -644,7 +635,6 @@ __global__ void __launch_bounds__(256, 2) k_point_front(FrontArgs a) {  // two w
         }
         lds_barrier();  // the Wk sums are consumed: their LDS becomes the record staging buffer
       }
-      mark();  // 6: intrinsics records
       // ---- pose entry records: U_a = (Jc' ^T Jp') Gi^T (6 x 3), e_a = U_a h ----
       for (int base = o0; base < o1; base += kFrontObs) {
         const int o = base + tid;
@@ -674,7 +664,6 @@ __global__ void __launch_bounds__(256, 2) k_point_front(FrontArgs a) {  // two w
             rec[18 + e] = u0 * g[6] + u1 * g[7] + u2 * g[8];
           }
         }
-        mark();  // 7: pose records in registers
         const long long lim = (long long)o1 * kPoseRec;
         // staged through LDS (pitch 25), coalesced stores: the whole window at once where the buffer holds 256 records,
         // else in two halves
@@ -698,14 +687,6 @@ __global__ void __launch_bounds__(256, 2) k_point_front(FrontArgs a) {  // two w
     } else {
       lds_barrier();  // (the next tile re-initialises the sums)
     }
-    mark();  // 8: records stored
-  }
-  if constexpr (TRACE) {
-    if (a.trace && (tid & 63) == 0 && blockIdx.x < 16384) {  // one line per wave: [n, stamps...] (single-tile work-groups)
-      long long* out = a.trace + ((size_t)blockIdx.x * 4 + (tid >> 6)) * 16;
-      out[0] = nstamp;
-      for (int i = 0; i < nstamp; ++i) out[1 + i] = stamp[i];
-    }
   }
   const double tot = block_sum_256(cost, s_red);
   if (tid == 0) w.cost_partial[blockIdx.x] = tot;
@@ -723,56 +704,20 @@ void launch_point_front(hipStream_t st, const FrontArgs& a, int kmax_intr, bool 
   const bool mask = a.sw.pt_active != nullptr;
   int dev = 0;
   (void)hipGetDevice(&dev);
-  // MAVBA_FRONT_TRACE=<file>: the 5th entries launch (widest model, unmasked) records s_memtime stamps per wave
-  static const char* trace_file = std::getenv("MAVBA_FRONT_TRACE");
-  static int trace_calls = 0;
-  if (trace_file && entries && !mask && kmax_intr > 4 && kmax_intr <= 8 && ++trace_calls == 5) {
-    const size_t n = (size_t)16384 * 4 * 16;
-    long long* tr = nullptr;
-    (void)hipMalloc(reinterpret_cast<void**>(&tr), n * 8);
-    (void)hipMemsetAsync(tr, 0, n * 8, st);
-    FrontArgs b = a;
-    b.trace = tr;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_point_front<8, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)FrontShape<8>::BYTES);
-    hipLaunchKernelGGL((k_point_front<8, true, false, true>), dim3(grid), dim3(256), FrontShape<8>::BYTES, st, b);
-    std::vector<long long> h(n);
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpy(h.data(), tr, n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(tr);
-    if (FILE* fp = std::fopen(trace_file, "w")) {
-      for (int b2 = 0; b2 < std::min(grid, 16384); ++b2)
-        for (int wv = 0; wv < 4; ++wv) {
-          const long long* r = &h[((size_t)b2 * 4 + wv) * 16];
-          std::fprintf(fp, "%d %d", b2, wv);
-          for (int i = 0; i < (int)r[0]; ++i) std::fprintf(fp, " %lld", r[1 + i]);
-          std::fprintf(fp, "\n");
+  with_width_or_none(kmax_intr, [&](auto k) {
+    with_bool(entries, [&](auto e) {
+      with_bool(mask, [&](auto m) {
+        const auto kernel = &k_point_front<decltype(k)::value, decltype(e)::value, decltype(m)::value>;
+        constexpr size_t bytes = FrontShape<decltype(k)::value>::BYTES;
+        static bool configured[64] = {};  // per instantiation and device: more than 64 KiB of dynamic LDS has to be asked for
+        if (dev >= 0 && dev < 64 && !configured[dev]) {
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+          configured[dev] = true;
         }
-      std::fclose(fp);
-    }
-    return;
-  }
-#define MAVBA_FRONT_LAUNCH(K, E, M)                                                                                     \
-  {                                                                                                                     \
-    static bool configured[64] = {};  /* per device: more than 64 KiB of dynamic LDS has to be asked for */            \
-    if (dev >= 0 && dev < 64 && !configured[dev]) {                                                                     \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_point_front<K, E, M>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)FrontShape<K>::BYTES);                                                             \
-      configured[dev] = true;                                                                                           \
-    }                                                                                                                   \
-    hipLaunchKernelGGL((k_point_front<K, E, M>), dim3(grid), dim3(256), FrontShape<K>::BYTES, st, a);                   \
-  }
-#define MAVBA_FRONT_K(K)                                                                       \
-  {                                                                                            \
-    if (entries) { if (mask) MAVBA_FRONT_LAUNCH(K, true, true) else MAVBA_FRONT_LAUNCH(K, true, false) }   \
-    else { if (mask) MAVBA_FRONT_LAUNCH(K, false, true) else MAVBA_FRONT_LAUNCH(K, false, false) }         \
-  }
-  if (kmax_intr <= 0) MAVBA_FRONT_K(0)
-  else if (kmax_intr <= 4) MAVBA_FRONT_K(4)
-  else if (kmax_intr <= 8) MAVBA_FRONT_K(8)
-  else MAVBA_FRONT_K(9)
-#undef MAVBA_FRONT_K
-#undef MAVBA_FRONT_LAUNCH
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), bytes, st, a);
+      });
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -782,16 +727,15 @@ void launch_point_front(hipStream_t st, const FrontArgs& a, int kmax_intr, bool 
 //   PP = Jc^T Jc, Pg = Jc^T r, PI = Jc^T Jk, II = Jk^T Jk, Ig = Jk^T r.
 // One block per chunk; the image's camera record is block-uniform.
 // ---------------------------------------------------------------------------
-template <int K>
 __global__ void __launch_bounds__(256) k_camera_sweep(CamSweepArgs a) {
   if (!lm_spec_go(a.spec, nullptr)) return;  // (speculative evaluation: only behind an accepted step)
   __shared__ double s_red[4 * kSweepAcc];
-  camera_sweep_body<K>(a, blockIdx.x, s_red);  // (sweep_body.h)
+  camera_sweep_body(a, blockIdx.x, s_red);  // (sweep_body.h)
 }
 
 // K4 with free intrinsics: the same sums as ONE 16 x 16 Gram matrix per chunk on the matrix cores. Every observation
 // gives two weighted rows  v = w [ Jc(6) | Jk(9) | r ]  (16 entries); G = sum v^T v holds PP, PI, II in its pose /
-// intrinsics blocks and Pg, Ig in its last column. The vector kernel above keeps ~120 FP64 accumulators per lane (one
+// intrinsics blocks and Pg, Ig in its last column. A vector kernel for these sums keeps ~120 FP64 accumulators per lane (one
 // wave per SIMD, nothing hides the Jacobian arithmetic, and 135 wave reductions at the end); here the accumulators are
 // 4 registers, already summed over the wave. A lane's rows go through LDS (pitch 34 doubles: 16-byte writes, and
 // the operand reads of a matrix instruction - element l & 15 of row l >> 4 of two neighbouring observations - are two
@@ -806,12 +750,9 @@ __global__ void __launch_bounds__(256, 2) k_camera_sweep_gram(CamSweepArgs a) {
 void launch_camera_sweep(hipStream_t st, const CamSweepArgs& a, int kmax, bool any_intr_free) {
   if (a.num_chunks <= 0) return;
   const dim3 g(a.num_chunks), b(256);
-  // (with free intrinsics the vector form - k_camera_sweep<4 / 8 / 9>, ~120 accumulators per lane - was 0.133 against the Gram
-  // form's 0.074 ms at C3, round 2; its switch MAVBA_CAMSWEEP_VECTOR went in round 6, the template keeps the code)
-  if (!any_intr_free) hipLaunchKernelGGL((k_camera_sweep<0>), g, b, 0, st, a);  // 27 sums: the vector kernel is the cheaper one
-  else if (kmax <= 4) hipLaunchKernelGGL((k_camera_sweep_gram<4>), g, b, 0, st, a);
-  else if (kmax <= 8) hipLaunchKernelGGL((k_camera_sweep_gram<8>), g, b, 0, st, a);
-  else hipLaunchKernelGGL((k_camera_sweep_gram<9>), g, b, 0, st, a);
+  // (with free intrinsics a vector form with ~120 accumulators per lane was 0.133 against the Gram form's 0.074 ms at C3, round 2)
+  if (!any_intr_free) hipLaunchKernelGGL(k_camera_sweep, g, b, 0, st, a);  // 27 sums: the vector kernel is the cheaper one
+  else with_width(kmax, [&](auto k) { hipLaunchKernelGGL((k_camera_sweep_gram<decltype(k)::value>), g, b, 0, st, a); });
 }
 
 // Rotation priors: one lane per prior (reference bundle_adjustment.cc:72-111, :428-444).
@@ -876,15 +817,12 @@ __global__ void __launch_bounds__(1024) k_camera_reduce_cam(
     cam_rec[(size_t)c * kCamRec + e] = tot;
   }
 }
-void launch_camera_reduce(hipStream_t st, int NI, int NC, const int* img_chunk_start,
-                          const double* partial, const int* prior_start, const double* prior_res,
-                          const double* prior_jac, const int* cam_img_start, const int* cam_imgs,
-                          double* img_rec, double* cam_rec, double* img_intr_tmp, bool with_cams, const LmSpec& spec, const PartialRide& ride) {
-  if (NI > 0 || ride.n > 0)
-    hipLaunchKernelGGL(k_camera_reduce_img, dim3(NI + ride.n), dim3(64), 0, st, NI, img_chunk_start, partial,
-                       prior_start, prior_res, prior_jac, img_rec, img_intr_tmp, spec, ride);
-  if (NC > 0 && with_cams)  // (no free intrinsics: nobody reads the per-camera sums, they stay zero)
-    hipLaunchKernelGGL(k_camera_reduce_cam, dim3(NC), dim3(1024), 0, st, cam_img_start, cam_imgs, img_intr_tmp, cam_rec, spec);
+void launch_camera_reduce(hipStream_t st, const EvalTailArgs& a) {
+  if (a.NI > 0 || a.ride.n > 0)
+    hipLaunchKernelGGL(k_camera_reduce_img, dim3(a.NI + a.ride.n), dim3(64), 0, st, a.NI, a.img_chunk_start, a.cam_partial,
+                       a.prior_start, a.prior_res, a.prior_jac, a.img_rec, a.img_intr_tmp, a.spec, a.ride);
+  if (a.NC > 0 && a.with_cams)  // (no free intrinsics: nobody reads the per-camera sums, they stay zero)
+    hipLaunchKernelGGL(k_camera_reduce_cam, dim3(a.NC), dim3(1024), 0, st, a.cam_img_start, a.cam_imgs, a.img_intr_tmp, a.cam_rec, a.spec);
 }
 
 // ---------------------------------------------------------------------------
@@ -948,16 +886,9 @@ void state_norms_grid(int NI, int NC, int NP, int* gp, int* gc) {
   *gp = std::min(512, (NP + 255) / 256);
   *gc = std::max(1, std::min(kStateNormsCamBlocks, (6 * NI + 9 * NC + 255) / 256));
 }
-void launch_state_norms(hipStream_t st, int NI, int NC, int NP, int NPs, bool cam_part,
-                        const unsigned char* pose_free, const unsigned char* intr_free,
-                        const unsigned char* pt_free, const double* poses, const double* intr,
-                        const double* points, const double* img_rec, const double* cam_rec,
-                        const double* gu, double* partial, int* grid_out, const LmSpec& spec) {
-  int gp, gc;
-  state_norms_grid(NI, NC, NP, &gp, &gc);
-  hipLaunchKernelGGL(k_state_norms, dim3(gp + gc), dim3(256), 0, st, NI, NC, NP, NPs, gp, cam_part ? 1 : 0,
-                     pose_free, intr_free, pt_free, poses, intr, points, img_rec, cam_rec, gu, partial, spec);
-  *grid_out = gp + gc;
+void launch_state_norms(hipStream_t st, const EvalTailArgs& a) {
+  hipLaunchKernelGGL(k_state_norms, dim3(a.gp + a.gc), dim3(256), 0, st, a.NI, a.NC, a.NP, a.NPs, a.gp, a.cam_part, a.pose_free,
+                     a.intr_free, a.pt_free, a.poses, a.intr, a.points, a.img_rec, a.cam_rec, a.gu, a.norm_partial, a.spec);
 }
 
 
@@ -966,11 +897,10 @@ void launch_state_norms(hipStream_t st, int NI, int NC, int NP, int NPs, bool ca
 // observation; records are transposed through LDS so the 192-byte records leave
 // the block as one contiguous, fully coalesced 48 KB store.
 // ---------------------------------------------------------------------------
-// FACTOR: the point's damped 3x3 block - C_p = S_p Cu S_p + D_p^2, C_p = G G^T, Gi = G^-1, h = Gi (S_p gu); the Schur
+// The point's damped 3x3 block - C_p = S_p Cu S_p + D_p^2, C_p = G G^T, Gi = G^-1, h = Gi (S_p gu); the Schur
 // eliminator's e-block step, D^2 = clamp(diag(Js^T Js)) / radius - is factorised HERE (by every observation of the point
 // - 9 + 3 values in instead of 6 + 3, ~100 instructions in an HBM-bound kernel) and its first observation stores Gi and h
 // for the later kernels: one launch less per linear solve.
-template <bool FACTOR>
 __global__ void __launch_bounds__(256) k_entries_pose(
     int N, int Nstride, int NPs, const int* __restrict__ obs_img, const int* __restrict__ obs_pt,
     const unsigned char* __restrict__ pt_free, const double* __restrict__ Jc, const double* __restrict__ Jp,
@@ -986,44 +916,35 @@ __global__ void __launch_bounds__(256) k_entries_pose(
   if (o < N) {
     const int p = obs_pt[o];
     const bool fr = pt_free[p] != 0;
-    if constexpr (FACTOR) {
-      if (!fr && o == pt_start[p]) {
+    if (!fr && o == pt_start[p]) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) Gi[k * NPs + p] = 0.0;
+      for (int k = 0; k < 6; ++k) Gi[k * NPs + p] = 0.0;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) h[k * NPs + p] = 0.0;
-      }
+      for (int k = 0; k < 3; ++k) h[k * NPs + p] = 0.0;
     }
     if (fr) {
       const int im = obs_img[o];
       double sp[3], G[6], hh[3], jp[6];
 #pragma unroll
       for (int k = 0; k < 3; ++k) sp[k] = scale_pt[k * NPs + p];
-      if constexpr (FACTOR) {
-        double C[6];
-        C[0] = sp[0] * sp[0] * Cu[p];           C[1] = sp[0] * sp[1] * Cu[NPs + p];     C[2] = sp[0] * sp[2] * Cu[2 * NPs + p];
-        C[3] = sp[1] * sp[1] * Cu[3 * NPs + p]; C[4] = sp[1] * sp[2] * Cu[4 * NPs + p]; C[5] = sp[2] * sp[2] * Cu[5 * NPs + p];
-        C[0] += clampd(C[0], dmin, dmax) / radius;
-        C[3] += clampd(C[3], dmin, dmax) / radius;
-        C[5] += clampd(C[5], dmin, dmax) / radius;
-        const bool ok = chol3_inv(C, G);
-        const double gs[3] = {sp[0] * gu[p], sp[1] * gu[NPs + p], sp[2] * gu[2 * NPs + p]};
-        gi_mul(G, gs, hh);
-        if (o == pt_start[p]) {
-          bool fin = ok;
+      double C[6];
+      C[0] = sp[0] * sp[0] * Cu[p];           C[1] = sp[0] * sp[1] * Cu[NPs + p];     C[2] = sp[0] * sp[2] * Cu[2 * NPs + p];
+      C[3] = sp[1] * sp[1] * Cu[3 * NPs + p]; C[4] = sp[1] * sp[2] * Cu[4 * NPs + p]; C[5] = sp[2] * sp[2] * Cu[5 * NPs + p];
+      C[0] += clampd(C[0], dmin, dmax) / radius;
+      C[3] += clampd(C[3], dmin, dmax) / radius;
+      C[5] += clampd(C[5], dmin, dmax) / radius;
+      const bool ok = chol3_inv(C, G);
+      const double gs[3] = {sp[0] * gu[p], sp[1] * gu[NPs + p], sp[2] * gu[2 * NPs + p]};
+      gi_mul(G, gs, hh);
+      if (o == pt_start[p]) {
+        bool fin = ok;
 #pragma unroll
-          for (int k = 0; k < 6; ++k) fin = fin && isfinite(G[k]);
-          if (!fin) atomicAdd(fail, 1.0);
+        for (int k = 0; k < 6; ++k) fin = fin && isfinite(G[k]);
+        if (!fin) atomicAdd(fail, 1.0);
 #pragma unroll
-          for (int k = 0; k < 6; ++k) Gi[k * NPs + p] = G[k];
+        for (int k = 0; k < 6; ++k) Gi[k * NPs + p] = G[k];
 #pragma unroll
-          for (int k = 0; k < 3; ++k) h[k * NPs + p] = hh[k];
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) hh[k] = h[k * NPs + p];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) G[k] = Gi[k * NPs + p];
+        for (int k = 0; k < 3; ++k) h[k * NPs + p] = hh[k];
       }
 #pragma unroll
       for (int row = 0; row < 2; ++row)
@@ -1053,21 +974,13 @@ __global__ void __launch_bounds__(256) k_entries_pose(
     if (base + i < lim) Epose[base + i] = s_rec[t * 25 + k];
   }
 }
-void launch_entries_pose(hipStream_t st, int N, int Nstride, int NPs, const int* obs_img,
-                         const int* obs_pt, const unsigned char* pt_free, const double* Jc,
-                         const double* Jp, const double* scale_cam, const double* scale_pt,
-                         double* Gi, double* h, double* Epose) {
-  if (N <= 0) return;
-  hipLaunchKernelGGL((k_entries_pose<false>), dim3((N + 255) / 256), dim3(256), 0, st, N, Nstride, NPs, obs_img, obs_pt,
-                     pt_free, Jc, Jp, scale_cam, scale_pt, Gi, h, Epose, nullptr, nullptr, nullptr, 1.0, 0.0, 0.0, nullptr);
-}
 // k_point_factor + k_entries_pose in one launch (points without observations keep whatever Gi / h hold: nothing reads them)
 void launch_factor_entries_pose(hipStream_t st, int N, int Nstride, int NPs, const int* obs_img, const int* obs_pt,
                                 const unsigned char* pt_free, const double* Jc, const double* Jp, const double* scale_cam,
                                 const double* scale_pt, double* Gi, double* h, double* Epose, const int* pt_start,
                                 const double* Cu, const double* gu, double radius, double dmin, double dmax, double* fail) {
   if (N <= 0) return;
-  hipLaunchKernelGGL((k_entries_pose<true>), dim3((N + 255) / 256), dim3(256), 0, st, N, Nstride, NPs, obs_img, obs_pt,
+  hipLaunchKernelGGL(k_entries_pose, dim3((N + 255) / 256), dim3(256), 0, st, N, Nstride, NPs, obs_img, obs_pt,
                      pt_free, Jc, Jp, scale_cam, scale_pt, Gi, h, Epose, pt_start, Cu, gu, radius, dmin, dmax, fail);
 }
 
@@ -1168,7 +1081,7 @@ __global__ void __launch_bounds__(256) k_schur_chunks(int num_chunks, const Schu
 // ---------------------------------------------------------------------------
 // Schur clusters (layout in internal.h): one work-group per cluster. The stacked entry matrix E of a batch
 // of kClBatch points is built in LDS (rows x 96 columns, pitch 100 -> conflict-free operand reads), and
-// S_cl += E E^T runs on v_mfma_f64_16x16x4_f64: the lower 16x16 tiles (36 for 128 rows, 21 for 96) are dealt
+// S_cl += E E^T runs on v_mfma_f64_16x16x4_f64: the lower 16x16 tiles (36 for 128 rows) are dealt
 // round-robin to the 4 waves; both operands of a tile are rows of E, so a k-step costs NT LDS reads and <= 9
 // matrix instructions per wave. 53 KB of LDS -> three work-groups per CU: one fetches its next batch while
 // the others keep the matrix cores busy. Every entry record is read from HBM exactly once per linear solve.
@@ -1177,11 +1090,10 @@ namespace {
 typedef double cl_d4 __attribute__((ext_vector_type(4)));
 constexpr int kClK = 3 * kClBatch, kClPitch = kClK + 2;  // (2 * pitch) mod 64 dwords = 4: the 32 lanes of a half-wave's operand read hit 64 different banks
 constexpr int kClThreads = 512, kClWaves = kClThreads / 64;  // two waves per SIMD: with one, every instruction of the clear / scatter / fetch phases shows its full latency (~10 cycles per instruction measured)
-template <int I, int C>
-struct ClShape {
-  static constexpr int images = I, cams = C, cam_row0 = 6 * I, hrow = 6 * I + 9 * C, rows = (hrow + 16) / 16 * 16;
+struct ClShape {  // the one cluster shape, 16 images x 3 cameras (internal.h)
+  static constexpr int images = kClImagesMax, cam_row0 = kClCamRow0, hrow = kClHRow, rows = kClRows;
   static constexpr int NT = rows / 16, tiles = NT * (NT + 1) / 2, acc = (tiles + kClWaves - 1) / kClWaves;
-  static constexpr int tab_ip = I * (I + 1) / 2, tab_ii = tab_ip + C * I, tab = tab_ii + C * (C + 1) / 2;
+  static constexpr int tab_ip = kClTabIP, tab_ii = kClTabII, tab = kClTab;
 };
 // false: small batches, two work-groups per CU that hide each other's latencies; true: one work-group per CU that
 // prefetches its next batch and double-buffers the operand reads itself
@@ -1402,20 +1314,14 @@ __device__ __forceinline__ void cluster_overflow(double* __restrict__ E, int tid
 }
 }  // namespace
 
-template <class SH, bool TRACE>
 __global__ void __launch_bounds__(kClThreads, kClPipelined ? 1 : 2) k_schur_clusters(
     const SchurCluster* __restrict__ clusters, const int* __restrict__ tabs, const int* __restrict__ pt_start,
     const int* __restrict__ q_start, const unsigned short* __restrict__ obs_meta,
     const unsigned short* __restrict__ q_meta, const unsigned char* __restrict__ pt_clustered,
     const double* __restrict__ Epose, const double* __restrict__ Eintr, const double* __restrict__ h, int NPs,
-    double* __restrict__ part_pp, double* __restrict__ part_ip, double* __restrict__ part_ii,
-    long long* __restrict__ trace) {
+    double* __restrict__ part_pp, double* __restrict__ part_ip, double* __restrict__ part_ii) {
+  using SH = ClShape;
   __shared__ __attribute__((aligned(16))) double E[SH::rows * kClPitch];
-  // (TRACE: a separate instantiation - the 24 stamps are 48 registers the production kernel needs for itself)
-  long long stamp[TRACE ? 24 : 1];
-  int nstamp = 0;
-  auto mark = [&]() { if constexpr (TRACE) { if (nstamp < 24) stamp[nstamp++] = (long long)__builtin_amdgcn_s_memtime(); } };
-  mark();
   __shared__ int s_bounds[2][kClMaxBatches + 1];  // first observation / intrinsics entry of every batch
   __shared__ int s_tab[SH::tab];
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
@@ -1455,19 +1361,16 @@ __global__ void __launch_bounds__(kClThreads, kClPipelined ? 1 : 2) k_schur_clus
     if constexpr (!kClPipelined) fetch(bi);  // all loads of the batch are in flight while E is cleared
     for (int i = tid; i < SH::rows * kClPitch / 2; i += kClThreads) reinterpret_cast<double2*>(E)[i] = make_double2(0.0, 0.0);
     __syncthreads();
-    mark();
     cluster_scatter(RP, PP, E, 0, 6, s_bounds[0][bi + 1] - s_bounds[0][bi]);
     cluster_scatter(RQ, PQ, E, SH::cam_row0, 9, s_bounds[1][bi + 1] - s_bounds[1][bi]);
     if (hon) E[SH::hrow * kClPitch + tid] = hv;
     cluster_overflow<kPoseRec, 18, kClChunk>(E, tid, s_bounds[0][bi], s_bounds[0][bi + 1] - s_bounds[0][bi], 0, 6, obs_meta, Epose);
     cluster_overflow<kIntrRec, 27, kClQChunk>(E, tid, s_bounds[1][bi], s_bounds[1][bi + 1] - s_bounds[1][bi], SH::cam_row0, 9, q_meta, Eintr);
     __syncthreads();
-    mark();
     if constexpr (kClPipelined) {
       if (bi + 1 < nbatch) fetch(bi + 1);  // travels while the matrix cores work on this batch
       __builtin_amdgcn_sched_barrier(0);   // (keep the loads here: the scheduler would sink them to their use)
     }
-    mark();
     switch (wv) {
       case 0: cluster_mfma<SH, 0>(E, lane, acc); break;
       case 1: cluster_mfma<SH, 1>(E, lane, acc); break;
@@ -1478,9 +1381,7 @@ __global__ void __launch_bounds__(kClThreads, kClPipelined ? 1 : 2) k_schur_clus
       case 6: cluster_mfma<SH, 6>(E, lane, acc); break;
       default: cluster_mfma<SH, 7>(E, lane, acc); break;
     }
-    mark();
     __syncthreads();
-    mark();
   }
   const int* tab = s_tab;
   switch (wv) {
@@ -1493,54 +1394,17 @@ __global__ void __launch_bounds__(kClThreads, kClPipelined ? 1 : 2) k_schur_clus
     case 6: cluster_emit<SH, 6>(lane, acc, tab, part_pp, part_ip, part_ii); break;
     default: cluster_emit<SH, 7>(lane, acc, tab, part_pp, part_ip, part_ii); break;
   }
-  mark();
-  if constexpr (TRACE) {
-    if (trace && (tid & 63) == 0 && wv < 4 && blockIdx.x < 4096) {  // one line per wave (the first four): [n, stamps...]
-      long long* out = trace + ((size_t)blockIdx.x * 4 + wv) * 32;
-      out[0] = nstamp;
-      for (int i = 0; i < nstamp; ++i) out[1 + i] = stamp[i];
-    }
-  }
 }
-#define MAVBA_CL_S12 ClShape<12, 2>
-#define MAVBA_CL_S16 ClShape<16, 3>
-void launch_schur_clusters(hipStream_t st, ClusterShape shape, int num_clusters, const SchurCluster* clusters, const int* tab,
+void launch_schur_clusters(hipStream_t st, int num_clusters, const SchurCluster* clusters, const int* tab,
                            const int* pt_start, const int* q_start, const unsigned short* obs_meta,
                            const unsigned short* q_meta, const unsigned char* pt_clustered, const double* Epose,
                            const double* Eintr, const double* h, int NPs, double* part_pp, double* part_ip,
                            double* part_ii) {
   if (num_clusters <= 0) return;
-  // MAVBA_CLUSTER_TRACE=<file>: the 5th launch of the process records s_memtime stamps per wave (debugging aid)
-  long long* trace = nullptr;
-  static int calls = 0;
-  static const char* trace_file = std::getenv("MAVBA_CLUSTER_TRACE");
-  const size_t trace_n = (size_t)4096 * 4 * 32;
-  if (trace_file && ++calls == 5) { (void)hipMalloc(reinterpret_cast<void**>(&trace), trace_n * 8); (void)hipMemsetAsync(trace, 0, trace_n * 8, st); }
-#define MAVBA_CL_LAUNCH(SHAPE, TR)                                                                                                    \
-  hipLaunchKernelGGL((k_schur_clusters<SHAPE, TR>), dim3(num_clusters), dim3(kClThreads), 0, st, clusters, tab, pt_start, q_start, obs_meta, \
-                     q_meta, pt_clustered, Epose, Eintr, h, NPs, part_pp, part_ip, part_ii, trace)
-  if (shape.images == 12) { if (trace) MAVBA_CL_LAUNCH(MAVBA_CL_S12, true); else MAVBA_CL_LAUNCH(MAVBA_CL_S12, false); }
-  else { if (trace) MAVBA_CL_LAUNCH(MAVBA_CL_S16, true); else MAVBA_CL_LAUNCH(MAVBA_CL_S16, false); }
-#undef MAVBA_CL_LAUNCH
-  if (trace) {
-    std::vector<long long> hst(trace_n);
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpy(hst.data(), trace, trace_n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(trace);
-    if (FILE* f = std::fopen(trace_file, "w")) {
-      for (int b = 0; b < std::min(num_clusters, 4096); ++b)
-        for (int w = 0; w < 4; ++w) {
-          const long long* r = &hst[((size_t)b * 4 + w) * 32];
-          std::fprintf(f, "%d %d", b, w);
-          for (int i = 0; i < (int)r[0]; ++i) std::fprintf(f, " %lld", r[1 + i]);
-          std::fprintf(f, "\n");
-        }
-      std::fclose(f);
-    }
-  }
+  hipLaunchKernelGGL(k_schur_clusters, dim3(num_clusters), dim3(kClThreads), 0, st, clusters, tab, pt_start, q_start, obs_meta,
+                     q_meta, pt_clustered, Epose, Eintr, h, NPs, part_pp, part_ip, part_ii);
 }
 
-int schur_partial_stride(int kind) { return kind == BLK_PP ? 42 : kind == BLK_IP ? 54 : 90; }
 void launch_schur_chunks(hipStream_t st, int kind, int num_chunks, const SchurChunk* chunks,
                          const int2* terms, const double* Epose, const double* Eintr, double* partial) {
   if (num_chunks <= 0) return;
@@ -1575,7 +1439,7 @@ __device__ __forceinline__ double strided_sum16(const double* __restrict__ part,
 // one task = one 64-lane group (also run as extra work-groups of k_camera_reduce_img / k_eval_head: PartialRide)
 __device__ void partial_reduce_task(const PartialReduce T, int lane, double* part_pp, double* part_ip, double* part_ii) {
   double* part = T.kind == BLK_PP ? part_pp : T.kind == BLK_IP ? part_ip : part_ii;
-  const int PS = T.kind == BLK_PP ? 42 : T.kind == BLK_IP ? 54 : 90;
+  const int PS = schur_partial_stride(T.kind);
   for (int idx = lane; idx < PS; idx += 64) part[(size_t)T.dst * PS + idx] = strided_sum16(part, PS, idx, T.src_begin, T.src_end);
 }
 __global__ void __launch_bounds__(256) k_partial_reduce(int num_tasks, const PartialReduce* __restrict__ tasks,
@@ -1944,38 +1808,10 @@ __global__ void __launch_bounds__(256) k_update_cameras(
   update_cameras_body(blockIdx.x, NI, NC, cam_part, radius, dmin, dmax, y, scale_cam, img_rec, cam_rec, poses, intr, cand_poses, cand_intr,
                       delta_cam, partial3, cand_camrec, s_red);
 }
-void launch_update_cameras(hipStream_t st, int NI, int NC, bool cam_part, double radius, double dmin,
-                           double dmax, const double* y, const double* scale_cam,
-                           const double* img_rec, const double* cam_rec, const double* poses,
-                           const double* intr, double* cand_poses, double* cand_intr,
-                           double* delta_cam, double* partial3, double* cand_camrec) {
-  hipLaunchKernelGGL(k_update_cameras, dim3(update_cameras_groups(NI)), dim3(256), 0, st, NI, NC, cam_part ? 1 : 0, radius, dmin,
-                     dmax, y, scale_cam, img_rec, cam_rec, poses, intr, cand_poses, cand_intr, delta_cam, partial3, cand_camrec);
-}
-
-// out[c] (op)= reduce over rows of partial[row*stride + c]; single block, fixed order.
-__global__ void __launch_bounds__(256) k_reduce_cols(const double* __restrict__ partial, int rows, int cols,
-                                                     int stride, unsigned max_mask, double* __restrict__ out,
-                                                     int accumulate) {
-  __shared__ double s_red[4];
-  for (int c = 0; c < cols; ++c) {
-    const bool mx = (max_mask >> c) & 1u;
-    double v = 0.0;
-    for (int r = threadIdx.x; r < rows; r += 256) {
-      const double x = partial[(size_t)r * stride + c];
-      v = mx ? fmax(v, x) : v + x;
-    }
-    const double t = mx ? block_max_256(v, s_red) : block_sum_256(v, s_red);
-    if (threadIdx.x == 0) {
-      if (accumulate) out[c] = mx ? fmax(out[c], t) : out[c] + t;
-      else out[c] = t;
-    }
-    __syncthreads();
-  }
-}
-void launch_reduce_cols(hipStream_t st, const double* partial, int rows, int cols, int stride,
-                        unsigned max_mask, double* out, bool accumulate) {
-  hipLaunchKernelGGL(k_reduce_cols, dim3(1), dim3(256), 0, st, partial, rows, cols, stride, max_mask, out, accumulate ? 1 : 0);
+void launch_update_cameras(hipStream_t st, const CamUpdateArgs& u, const double* y) {
+  hipLaunchKernelGGL(k_update_cameras, dim3(update_cameras_groups(u.NI)), dim3(256), 0, st, u.NI, u.NC, u.cam_part, u.radius, u.dmin,
+                     u.dmax, y, u.scale_cam, u.img_rec, u.cam_rec, u.poses, u.intr, u.cand_poses, u.cand_intr, u.delta_cam, u.partial3,
+                     u.cand_camrec);
 }
 
 // Several independent single-block reductions in ONE launch (the scalars of an LM phase): block b handles task b,
@@ -1998,55 +1834,20 @@ __global__ void __launch_bounds__(1024) k_lm_tail(ReduceTasks T, int n, LmSpec s
 }
 // The tail of an evaluation for a small problem in ONE work-group of 1024 lanes: per-image sums (one lane per element),
 // per-camera sums, norms (four of k_state_norms' groups at a time), the three scalar reductions (side by side) -
-// k_camera_reduce_img + k_camera_reduce_cam + k_state_norms + k_reduce_tasks: 17 us of launches for ~4 us of work.
-constexpr int kEvalSmallMaxGroups = 40;  // 8192 points / 256 + camera groups
-__global__ void __launch_bounds__(1024) k_eval_small(EvalSmallArgs a) {
-  __shared__ double s_part[16][64];
-  __shared__ double s_w[kEvalSmallMaxGroups][2][4];
-  __shared__ double s_t[4][2][4];
+// k_camera_reduce_img + k_camera_reduce_cam + k_state_norms + k_reduce_tasks: 17 us of launches for ~4 us of work
+// (eval_tail_body, lm_bodies.h).
+__global__ void __launch_bounds__(1024) k_eval_small(EvalTailArgs a) {
   if (!lm_spec_go(a.spec, nullptr)) return;
-  const int tid = threadIdx.x, g = tid >> 8, lt = tid & 255, wv = (tid >> 6) & 3, lane = tid & 63;
-  for (int q = tid; q < a.NI * kSweepAcc; q += 1024)
-    camera_reduce_img_elem(q / kSweepAcc, q % kSweepAcc, a.img_chunk_start, a.cam_partial, a.prior_start, a.prior_res, a.prior_jac, a.img_rec,
-                           a.img_intr_tmp);
-  __syncthreads();
-  if (a.with_cams) {
-    for (int c = 0; c < a.NC; ++c) {
-      if (lane < kCamRec) s_part[tid >> 6][lane] = camera_reduce_cam_part(c, tid >> 6, lane, a.cam_img_start, a.cam_imgs, a.img_intr_tmp);
-      __syncthreads();
-      if (tid < kCamRec) {
-        double tot = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) tot += s_part[k][tid];
-        a.cam_rec[(size_t)c * kCamRec + tid] = tot;
-      }
-      __syncthreads();
-    }
-  }
-  const int nvb = a.gp + a.gc;
-  for (int vb0 = 0; vb0 < nvb; vb0 += 4) {
-    const int vb = vb0 + g;
-    if (vb < nvb) {
-      double gmax, x2;
-      state_norms_local(vb, lt, a.gp, a.gc, a.NI, a.NC, a.NP, a.NPs, a.cam_part, a.pose_free, a.intr_free, a.pt_free, a.poses, a.intr, a.points,
-                        a.img_rec, a.cam_rec, a.gu, gmax, x2);
-      const double m = wave_max(gmax), sum = wave_sum(x2);
-      if (lane == 0) { s_w[vb][0][wv] = m; s_w[vb][1][wv] = sum; }
-    }
-  }
-  __syncthreads();
-  if (tid < nvb) { a.norm_partial[2 * tid] = group4_max(s_w[tid][0]); a.norm_partial[2 * tid + 1] = group4_sum(s_w[tid][1]); }
-  __syncthreads();
-  reduce_tasks_grouped(a.T, a.num_tasks, s_t);
+  eval_tail_body<true>(a);
 }
-void launch_eval_small(hipStream_t st, const EvalSmallArgs& a) { hipLaunchKernelGGL(k_eval_small, dim3(1), dim3(1024), 0, st, a); }
+void launch_eval_small(hipStream_t st, const EvalTailArgs& a) { hipLaunchKernelGGL(k_eval_small, dim3(1), dim3(1024), 0, st, a); }
 // Round 5: the tail of an evaluation of a LARGE problem was four dependent launches of 5-7 us each (k_camera_reduce_img,
 // k_camera_reduce_cam, k_state_norms, k_reduce_tasks) for a few microseconds of work. Two launches: k_eval_head - the
 // per-image sums (four images per 256-lane work-group) and the POINTS' norm groups, independent of each other, in one
 // grid -, k_eval_tail - one 1024-lane work-group: per-camera sums, the CAMERAS' norm groups (they need those sums),
 // the three reductions over the partials of both kernels. The same device functions in the same order as the launches they
 // replace (lm_bodies.h): bit-identical results. Not with shards (the camera sums are all-reduced between the two halves).
-__global__ void __launch_bounds__(256) k_eval_head(EvalSmallArgs a, int img_blocks) {
+__global__ void __launch_bounds__(256) k_eval_head(EvalTailArgs a, int img_blocks) {
   __shared__ double s_red[4];
   if (!lm_spec_go(a.spec, nullptr)) return;
   if ((int)blockIdx.x < img_blocks) {
@@ -2062,52 +1863,17 @@ __global__ void __launch_bounds__(256) k_eval_head(EvalSmallArgs a, int img_bloc
   state_norms_body(blockIdx.x - img_blocks, a.gp, a.gc, a.NI, a.NC, a.NP, a.NPs, a.cam_part, a.pose_free, a.intr_free, a.pt_free, a.poses, a.intr,
                    a.points, a.img_rec, a.cam_rec, a.gu, a.norm_partial, s_red);
 }
-__global__ void __launch_bounds__(1024) k_eval_tail(EvalSmallArgs a) {
-  __shared__ double s_part[16][64];
-  __shared__ double s_w[kStateNormsCamBlocks][2][4];
-  __shared__ double s_t[4][2][4];
+__global__ void __launch_bounds__(1024) k_eval_tail(EvalTailArgs a) {
   if (!lm_spec_go(a.spec, nullptr)) return;
-  const int tid = threadIdx.x, g = tid >> 8, lt = tid & 255, wv = (tid >> 6) & 3, lane = tid & 63;
-  if (a.with_cams) {
-    for (int c = 0; c < a.NC; ++c) {
-      if (lane < kCamRec) s_part[tid >> 6][lane] = camera_reduce_cam_part(c, tid >> 6, lane, a.cam_img_start, a.cam_imgs, a.img_intr_tmp);
-      __syncthreads();
-      if (tid < kCamRec) {
-        double tot = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) tot += s_part[k][tid];
-        a.cam_rec[(size_t)c * kCamRec + tid] = tot;
-      }
-      __syncthreads();
-    }
-  }
-  const int nvb = a.gp + a.gc;
-  for (int vb0 = a.first_group; vb0 < nvb; vb0 += 4) {
-    const int vb = vb0 + g;
-    if (vb < nvb) {
-      double gmax, x2;
-      state_norms_local(vb, lt, a.gp, a.gc, a.NI, a.NC, a.NP, a.NPs, a.cam_part, a.pose_free, a.intr_free, a.pt_free, a.poses, a.intr, a.points,
-                        a.img_rec, a.cam_rec, a.gu, gmax, x2);
-      const double m = wave_max(gmax), sum = wave_sum(x2);
-      if (lane == 0) { s_w[vb - a.first_group][0][wv] = m; s_w[vb - a.first_group][1][wv] = sum; }
-    }
-  }
-  __syncthreads();
-  if (tid < nvb - a.first_group) {
-    a.norm_partial[2 * (a.first_group + tid)] = group4_max(s_w[tid][0]);
-    a.norm_partial[2 * (a.first_group + tid) + 1] = group4_sum(s_w[tid][1]);
-  }
-  __syncthreads();
-  reduce_tasks_grouped(a.T, a.num_tasks, s_t);
+  eval_tail_body<false>(a);
 }
-void launch_eval_head_tail(hipStream_t st, const EvalSmallArgs& a) {
+void launch_eval_head_tail(hipStream_t st, const EvalTailArgs& a) {
   const int img_blocks = (a.NI + 3) / 4;
   hipLaunchKernelGGL(k_eval_head, dim3(img_blocks + a.gp + (a.ride.n + 3) / 4), dim3(256), 0, st, a, img_blocks);
-  EvalSmallArgs b = a;
+  EvalTailArgs b = a;
   b.first_group = a.gp;
   hipLaunchKernelGGL(k_eval_tail, dim3(1), dim3(1024), 0, st, b);
 }
-bool eval_head_tail_fits(int gc) { return gc <= kStateNormsCamBlocks; }
 void launch_lm_tail(hipStream_t st, const ReduceTasks& T, int n, const LmSpec& spec, double* dec, double* host_pub, double seq, double* fail_slots) {
   if (n > 4) {  // (the merged kernel runs at most four reductions side by side)
     launch_reduce_tasks(st, T, n);

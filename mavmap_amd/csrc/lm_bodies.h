@@ -5,7 +5,7 @@
 // factorisation, the camera update, the decision. Each body below is what one work-group (or one wave) of the kernel of
 // the same name does, with the work-group index as a parameter, so that
 //   - the multi-work-group kernels (kernels.hip) call it with blockIdx.x - large problems are unchanged -, and
-//   - the merged single-work-group kernels (k_eval_small, k_chol_small<true>, k_lm_tail) walk the same bodies in a loop:
+//   - the merged single-work-group kernels (k_eval_small, k_eval_tail, k_chol_small<true>, k_lm_tail) walk the same bodies in a loop:
 //     the same additions in the same order, bit-identical results, one launch instead of three to four.
 // Inside a merged kernel a body reads what an earlier body of the SAME work-group wrote to global memory (behind a
 // __syncthreads()): no pointer here is __restrict__, so the compiler can not turn such a read into a scalar / invariant load.
@@ -161,6 +161,55 @@ __device__ __forceinline__ void reduce_tasks_grouped(const ReduceTasks& T, int n
     *t.out = total;
   }
   __syncthreads();
+}
+
+// The tail of an evaluation in ONE 1024-lane work-group: (IMAGES: the per-image sums, one lane per element,) the per-camera
+// sums, k_state_norms' groups [a.first_group, a.gp + a.gc) four at a time, the scalar reductions side by side. IMAGES is
+// k_eval_small (everything, first_group = 0); without, k_eval_tail behind k_eval_head, which did the images and the points'
+// groups. At most kStateNormsCamBlocks groups are walked here (state_norms_grid: a local window has at most 32 + 2).
+template <bool IMAGES>
+__device__ __forceinline__ void eval_tail_body(const EvalTailArgs& a) {
+  __shared__ double s_part[16][64];
+  __shared__ double s_w[kStateNormsCamBlocks][2][4];
+  __shared__ double s_t[4][2][4];
+  const int tid = threadIdx.x, g = tid >> 8, lt = tid & 255, wv = (tid >> 6) & 3, lane = tid & 63;
+  if constexpr (IMAGES) {
+    for (int q = tid; q < a.NI * kSweepAcc; q += 1024)
+      camera_reduce_img_elem(q / kSweepAcc, q % kSweepAcc, a.img_chunk_start, a.cam_partial, a.prior_start, a.prior_res, a.prior_jac, a.img_rec,
+                             a.img_intr_tmp);
+    __syncthreads();
+  }
+  if (a.with_cams) {
+    for (int c = 0; c < a.NC; ++c) {
+      if (lane < kCamRec) s_part[tid >> 6][lane] = camera_reduce_cam_part(c, tid >> 6, lane, a.cam_img_start, a.cam_imgs, a.img_intr_tmp);
+      __syncthreads();
+      if (tid < kCamRec) {
+        double tot = 0.0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) tot += s_part[k][tid];
+        a.cam_rec[(size_t)c * kCamRec + tid] = tot;
+      }
+      __syncthreads();
+    }
+  }
+  const int nvb = a.gp + a.gc;
+  for (int vb0 = a.first_group; vb0 < nvb; vb0 += 4) {
+    const int vb = vb0 + g;
+    if (vb < nvb) {
+      double gmax, x2;
+      state_norms_local(vb, lt, a.gp, a.gc, a.NI, a.NC, a.NP, a.NPs, a.cam_part, a.pose_free, a.intr_free, a.pt_free, a.poses, a.intr, a.points,
+                        a.img_rec, a.cam_rec, a.gu, gmax, x2);
+      const double m = wave_max(gmax), sum = wave_sum(x2);
+      if (lane == 0) { s_w[vb - a.first_group][0][wv] = m; s_w[vb - a.first_group][1][wv] = sum; }
+    }
+  }
+  __syncthreads();
+  if (tid < nvb - a.first_group) {
+    a.norm_partial[2 * (a.first_group + tid)] = group4_max(s_w[tid][0]);
+    a.norm_partial[2 * (a.first_group + tid) + 1] = group4_sum(s_w[tid][1]);
+  }
+  __syncthreads();
+  reduce_tasks_grouped(a.T, a.num_tasks, s_t);
 }
 
 // Camera columns: step = -y, delta = s * step, candidate parameters. Work-group vb takes the images [42 vb, 42 vb + 42) -

@@ -34,6 +34,7 @@
 #include "dev_reduce.h"
 #include "lm_decide.h"
 #include "sweep_body.h"
+#include "launch_dispatch.h"
 
 // MAVBA_ROWS_SKIP (debug builds only, scripts/_dbg/rows_variants.sh): bit mask of parts left out to time the rest - wrong results.
 #ifndef MAVBA_ROWS_SKIP
@@ -47,8 +48,8 @@ constexpr int kF2Threads = 256, kF2Waves = 4;
 constexpr int kF2K = 3 * kRowsBatch, kF2Pitch = kF2K + 2;  // (2 * pitch) mod 64 dwords = 36: the 32 lanes of a half-wave's operand read hit 64 different banks
 static_assert(kRowsBatch == 16, "one point per 16-lane DPP row");
 static_assert((2 * kF2Pitch) % 8 == 4, "pitch must spread the 16 operand rows over all banks");
-// slot tables of a cluster: the 16 x 3 layout of ClusterShape{16, 3} for every row count
-constexpr int kF2TabIP = 136, kF2TabII = 184, kF2Tab = 190;
+// slot tables of a cluster: the 16 x 3 layout (internal.h) for every row count
+constexpr int kF2TabIP = kClTabIP, kF2TabII = kClTabII, kF2Tab = kClTab;
 
 // ---- DPP within a 16-lane row ----
 // (bound_ctrl: every control used here reads a lane of the row, so the "old" value is never kept - with bound_ctrl = 0 the
@@ -228,7 +229,7 @@ __device__ __forceinline__ void f2_write_blocks(const double* __restrict__ T, in
 // One launch for all row classes: the cluster's row count selects the instantiation of the batch loop (the registers and
 // the LDS of the kernel are those of the largest class either way: two work-groups per CU).
 // SWEEP (round 6, local windows with constant intrinsics): work-groups behind the clusters' run the camera sweep's chunks
-// (camera_sweep_body<0>, sweep_body.h) - the evaluation's other pass over the observations, independent of this one - so that
+// (camera_sweep_body, sweep_body.h) - the evaluation's other pass over the observations, independent of this one - so that
 // a 65 us iteration has one launch less; the sweep's LDS scratch is this kernel's entry matrix.
 struct RowsSweep { CamSweepArgs cs; int first; };  // first: number of cluster work-groups in front of the sweep's
 template <int KMAX, bool GENERIC, bool TRACE = false, bool SWEEP = false>
@@ -251,7 +252,7 @@ __global__ void __launch_bounds__(kF2Threads, 2) k_schur_rows(
   if constexpr (SWEEP) {
     static_assert(kF2Threads == 256 && SHMAX::rows * kF2Pitch >= 4 * kSweepAcc, "the sweep's chunk layout and scratch");
     if ((int)blockIdx.x >= sweep.first) {
-      if constexpr (KMAX == 0) camera_sweep_body<0>(sweep.cs, (int)blockIdx.x - sweep.first, E);
+      if constexpr (KMAX == 0) camera_sweep_body(sweep.cs, (int)blockIdx.x - sweep.first, E);
       else camera_sweep_gram_body<KMAX>(sweep.cs, (int)blockIdx.x - sweep.first, E);
       return;
     }
@@ -652,23 +653,13 @@ void launch_schur_rows(hipStream_t st, const FrontArgs& a, int kmax_intr, bool g
   if (num_clusters <= 0) return;
   RowsSweep sweep{};
   sweep.first = num_clusters;
-  if (with_sweep) {
-    // (the caller asks for it on local windows; the sweep's form follows the widest model like launch_camera_sweep's: the vector
-    // kernel's body without free intrinsics, the Gram form's with)
-    sweep.cs = *with_sweep;
-#define MAVBA_ROWS_SWEEP(K, G) hipLaunchKernelGGL((k_schur_rows<K, G, false, true>), dim3(num_clusters + with_sweep->num_chunks), dim3(kF2Threads), 0, st, a, \
-                                                 clusters, tab, cl_lists, obs_meta, lanemap, emit_map, part_pp, part_ip, part_ii, sweep)
-    if (kmax_intr <= 0) MAVBA_ROWS_SWEEP(0, true);
-    else if (kmax_intr <= 4) { if (generic) MAVBA_ROWS_SWEEP(4, true); else MAVBA_ROWS_SWEEP(4, false); }
-    else if (kmax_intr <= 8) { if (generic) MAVBA_ROWS_SWEEP(8, true); else MAVBA_ROWS_SWEEP(8, false); }
-    else MAVBA_ROWS_SWEEP(9, true);
-#undef MAVBA_ROWS_SWEEP
-    return;
-  }
+  // (the caller asks for the sweep on local windows; its form follows the widest model like launch_camera_sweep's: the vector
+  // kernel's body without free intrinsics, the Gram form's with)
+  if (with_sweep) sweep.cs = *with_sweep;
   // MAVBA_ROWS_TRACE=<file>: the 5th launch of the process (widest model <= 8) records s_memtime stamps per wave
   static const char* trace_file = std::getenv("MAVBA_ROWS_TRACE");
   static int trace_calls = 0;
-  if (trace_file && !generic && kmax_intr > 4 && kmax_intr <= 8 && ++trace_calls == 5) {
+  if (trace_file && !with_sweep && !generic && kmax_intr > 4 && kmax_intr <= 8 && ++trace_calls == 5) {
     const size_t trace_n = (size_t)4096 * kF2Waves * 16;
     long long* tr = nullptr;
     (void)hipMalloc(reinterpret_cast<void**>(&tr), trace_n * 8);
@@ -695,12 +686,18 @@ void launch_schur_rows(hipStream_t st, const FrontArgs& a, int kmax_intr, bool g
     }
     return;
   }
-#define MAVBA_ROWS(K, G) hipLaunchKernelGGL((k_schur_rows<K, G>), dim3(num_clusters), dim3(kF2Threads), 0, st, a, clusters, tab, cl_lists, obs_meta, lanemap, emit_map, part_pp, part_ip, part_ii, sweep)
-  if (kmax_intr <= 0) MAVBA_ROWS(0, true);
-  else if (kmax_intr <= 4) { if (generic) MAVBA_ROWS(4, true); else MAVBA_ROWS(4, false); }
-  else if (kmax_intr <= 8) { if (generic) MAVBA_ROWS(8, true); else MAVBA_ROWS(8, false); }
-  else MAVBA_ROWS(9, true);
-#undef MAVBA_ROWS
+  const int grid = num_clusters + (with_sweep ? with_sweep->num_chunks : 0);
+  with_width_or_none(kmax_intr, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    constexpr bool in_place = K == 4 || K == 8;  // (the in-place form of the intrinsics entries exists for these widths only)
+    with_bool(generic || !in_place, [&](auto g) {
+      with_bool(with_sweep != nullptr, [&](auto sw) {
+        if constexpr (decltype(g)::value || in_place)
+          hipLaunchKernelGGL((k_schur_rows<K, decltype(g)::value, false, decltype(sw)::value>), dim3(grid), dim3(kF2Threads), 0, st, a, clusters, tab,
+                             cl_lists, obs_meta, lanemap, emit_map, part_pp, part_ip, part_ii, sweep);
+      });
+    });
+  });
 }
 
 }  // namespace mavba

@@ -327,7 +327,6 @@ struct mavba_session {
   DevBuf<unsigned short> d_obs_meta, d_q_meta;
   DevBuf<unsigned char> d_pt_clustered;
   int num_clusters = 0, num_slots[3] = {0, 0, 0};
-  ClusterShape cl_shape{16, 3};
   long long clustered_points = 0, cluster_partials = 0;
   double cluster_flops = 0.0;
   DevBuf<int2> d_terms[3];
@@ -504,6 +503,8 @@ void intr_entries_on_device(const std::vector<unsigned char>& cam_active, std::v
   // candidate point - every kernel returns at once unless k_lm_snapshot accepted the step, the front end takes the radius
   // from its decision (next_radius only says "with entries")
   void evaluate_enqueue(double next_radius = -1.0, const LmSpec& spec = lm_spec_off());
+  EvalTailArgs eval_tail_args(const LmSpec& spec);  // the evaluation's tail at the current x (behind the front end / the sweeps)
+  CamUpdateArgs cam_update_args(double r);          // the candidate's camera update for trust-region radius r
   void launch_front(double r, bool entries, const LmSpec& spec = lm_spec_off(), const CamSweepArgs* with_sweep = nullptr);
   // ---- speculative evaluation (lm_decide.h) ----
   DevBuf<double> d_lm_dec;       // {code, radius} of k_lm_snapshot's decision

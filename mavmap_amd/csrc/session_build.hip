@@ -868,21 +868,12 @@ void mavba_session::finish_structure() {
   std::vector<unsigned char> pt_mode(NP, 0);
   std::vector<unsigned short> obs_meta((size_t)std::max(N, 1), 0xFFFFu), q_meta((size_t)std::max(Q, 1), 0xFFFFu);
   std::vector<SchurCluster> clusters;
-  std::vector<int> cl_imgs, cl_cams;  // [cluster][sh.images] / [cluster][sh.cams], ascending, -1 padded
-  {
-    // Cluster shape: 16 images x 3 cameras (128 rows, 36 tiles). MAVBA_CLUSTER_SHAPE=12 selects 12 x 2 (96 rows,
-    // 21 tiles): 42 % fewer matrix instructions per batch, but the smaller image list closes clusters earlier (C3:
-    // 2851 clusters of ~70 points instead of 1799 of ~110) and the per-cluster costs eat the gain - same 0.37 ms.
-    cl_shape = ClusterShape{16, 3};
-    if (const char* e = std::getenv("MAVBA_CLUSTER_SHAPE")) cl_shape = std::atoi(e) == 12 ? ClusterShape{12, 2} : ClusterShape{16, 3};
-  }
+  std::vector<int> cl_imgs, cl_cams;  // [cluster][kClImages] / [cluster][kClCams], ascending, -1 padded
   // The point order puts the points that can never be clustered (more than kTailObs observations, constant) behind all the
   // others (order_on_host / k_point_keys): clusters end where that tail begins.
   tail_begin = NP;
   while (tail_begin > 0 && (h_pt_start[tail_begin] - h_pt_start[tail_begin - 1] > kTailObs || h_pt_const_in[tail_begin - 1])) --tail_begin;
-  const ClusterShape sh = cl_shape;
-  const int kClTab = sh.tab(), kClTabPP = sh.tab_pp(), kClTabIP = sh.tab_ip(), kClTabII = sh.tab_ii();
-  const int kClImages = sh.images, kClCams = sh.cams;
+  constexpr int kClImages = kClImagesMax, kClCams = kClCamsMax;  // (one cluster shape, 16 x 3: internal.h)
   // Round 4: the clusters of k_schur_rows. The number of ROWS of a cluster's entry matrix decides what a batch costs (80
   // rows = 10 images + 2 cameras + h: 15 tiles of matrix instructions; 96 rows: 21; 128 rows: 36), so clusters are formed
   // from runs of points with one image set by estimated cost (do_range_rows) instead of "until 16 images are full". The
@@ -1102,11 +1093,11 @@ void mavba_session::finish_structure() {
     long long head_observed = 0, head_clustered = 0, all_clustered = 0;
     for (int p = 0; p < tail_begin; ++p) { head_observed += h_pt_start[p + 1] > h_pt_start[p]; head_clustered += pt_mode[p] == 1; }
     for (int p = 0; p < NP; ++p) all_clustered += pt_mode[p] == 1;
-    return front_ok && !no_fuse_env && cl_shape.images == 16 && !clusters.empty() && head_clustered == head_observed &&
+    return front_ok && !no_fuse_env && !clusters.empty() && head_clustered == head_observed &&
            all_clustered == head_clustered && (long long)clusters.size() <= kFrontMaxGrid;
   };
   rows_ok = false;
-  if (front_ok && !no_fuse_env && cl_shape.images == 16) {
+  if (front_ok && !no_fuse_env) {
     build_clusters(true);
     rows_ok = fusable();
   }
@@ -1120,7 +1111,7 @@ void mavba_session::finish_structure() {
       const int nt = kRowsClassNT[rows_class_of_rows(rows_count(cl_ni[c], cl_kr[c]))];
       cluster_flops += (double)((np + kRowsBatch - 1) / kRowsBatch) * (3 * kRowsBatch / 4) * (double)(nt * (nt + 1) / 2) * 2048.0;
     } else {
-      cluster_flops += (double)((np + kClBatch - 1) / kClBatch) * (3 * kClBatch / 4) * (double)((sh.rows() / 16) * (sh.rows() / 16 + 1) / 2) * 2048.0;
+      cluster_flops += (double)((np + kClBatch - 1) / kClBatch) * (3 * kClBatch / 4) * (double)((kClRows / 16) * (kClRows / 16 + 1) / 2) * 2048.0;
     }
   }
   // local indices of every clustered observation / intrinsics entry, and which blocks a cluster touches
@@ -1537,7 +1528,7 @@ void mavba_session::finish_structure() {
     long long head_observed = 0, head_clustered = 0;
     for (int p = 0; p < tail_begin; ++p) { head_observed += h_pt_start[p + 1] > h_pt_start[p]; head_clustered += pt_mode[p] == 1; }
     const bool no_fuse = std::getenv("MAVBA_NO_FUSE") != nullptr;  // (read per session: the tests switch paths)
-    fused_ok = front_ok && !no_fuse && cl_shape.images == 16 && num_clusters > 0 && head_clustered == head_observed &&
+    fused_ok = front_ok && !no_fuse && num_clusters > 0 && head_clustered == head_observed &&
                clustered_points == head_clustered && num_clusters <= kFrontMaxGrid;
     num_tail_tiles = 0;
     if (fused_ok && h_pt_start[NP] > h_pt_start[tail_begin]) {

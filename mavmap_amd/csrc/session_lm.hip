@@ -84,6 +84,38 @@ void mavba_session::launch_front(double r, bool entries, const LmSpec& spec, con
   front_radius = r;
 }
 
+// What the tail of an evaluation needs (EvalTailArgs, internal.h), for whichever route evaluate_enqueue takes. Behind the
+// front end: the cost's rows are those its last pass wrote.
+EvalTailArgs mavba_session::eval_tail_args(const LmSpec& spec) {
+  EvalTailArgs e;
+  e.NI = NI; e.NC = NC; e.NP = NP; e.NPs = NPs; e.with_cams = any_intr_free ? 1 : 0; e.cam_part = rank == 0 ? 1 : 0;
+  state_norms_grid(NI, NC, NP, &e.gp, &e.gc);
+  e.img_chunk_start = d_img_chunk_start.p; e.cam_partial = d_cam_partial.p;
+  e.prior_start = num_priors > 0 ? d_prior_start.p : nullptr; e.prior_res = d_prior_res.p; e.prior_jac = d_prior_jac.p;
+  e.cam_img_start = d_cam_img_start.p; e.cam_imgs = d_cam_imgs.p; e.img_rec = d_img_rec; e.cam_rec = d_cam_rec;
+  e.img_intr_tmp = d_img_intr_tmp.p;
+  e.pose_free = d_pose_free.p; e.intr_free = d_intr_free.p; e.pt_free = d_pt_free.p;
+  e.poses = d_poses.p; e.intr = d_intr.p; e.points = d_points.p; e.gu = d_gu.p; e.norm_partial = d_norm_partial.p;
+  const int rows = e.gp + e.gc;
+  e.T.t[0] = ReduceTask{d_norm_partial.p, rows, 2, 1, nullptr, 0, d_scal.p + SC_GRAD_MAX};
+  e.T.t[1] = ReduceTask{d_norm_partial.p + 1, rows, 2, 0, nullptr, 0, d_scal.p + SC_XNORM2};
+  e.T.t[2] = ReduceTask{d_sweep_partial.p, eval_cost_rows(), 1, 0, d_prior_cost.p, num_priors, d_scal.p + SC_COST};
+  e.num_tasks = 3;
+  e.spec = spec;
+  return e;
+}
+
+// The camera update of the candidate step for trust-region radius r (CamUpdateArgs, internal.h): its triples go behind the
+// point back-substitution's in d_step_partial; the candidate's camera records are written too (no separate cam_prepare launch).
+CamUpdateArgs mavba_session::cam_update_args(double r) {
+  CamUpdateArgs u;
+  u.NI = NI; u.NC = NC; u.cam_part = rank == 0 ? 1 : 0; u.radius = r; u.dmin = opt.min_lm_diagonal; u.dmax = opt.max_lm_diagonal;
+  u.scale_cam = d_scale_cam.p; u.img_rec = d_img_rec; u.cam_rec = d_cam_rec; u.poses = d_poses.p; u.intr = d_intr.p;
+  u.cand_poses = d_cposes.p; u.cand_intr = d_cintr.p; u.delta_cam = d_delta_cam.p;
+  u.partial3 = d_step_partial.p + 3 * (size_t)backsub_points_grid(NP); u.cand_camrec = d_ccamrec.p;
+  return u;
+}
+
 void mavba_session::evaluate_enqueue(double next_radius, const LmSpec& spec) {
   if (!camrec_current) timed("cam_prepare", [&] { launch_cam_prepare(st, NI, d_poses.p, d_camrec.p); });
   camrec_current = true;
@@ -130,64 +162,24 @@ void mavba_session::evaluate_enqueue(double next_radius, const LmSpec& spec) {
       launch_rot_prior(st, num_priors, d_prior_img.p, d_prior_R0.p, prior_weight, d_poses.p, d_prior_res.p,
                        d_prior_jac.p, d_prior_cost.p, spec);
     });
+  EvalTailArgs e = eval_tail_args(spec);
   if (scales_ready && merge_small()) {
     // a local window: per-image and per-camera sums, norms and the evaluation's three scalars by ONE work-group
-    timed("eval_small", [&] {
-      EvalSmallArgs e;
-      e.NI = NI; e.NC = NC; e.NP = NP; e.NPs = NPs; e.with_cams = any_intr_free ? 1 : 0; e.cam_part = rank == 0 ? 1 : 0;
-      state_norms_grid(NI, NC, NP, &e.gp, &e.gc);
-      e.img_chunk_start = d_img_chunk_start.p; e.cam_partial = d_cam_partial.p;
-      e.prior_start = num_priors > 0 ? d_prior_start.p : nullptr; e.prior_res = d_prior_res.p; e.prior_jac = d_prior_jac.p;
-      e.cam_img_start = d_cam_img_start.p; e.cam_imgs = d_cam_imgs.p; e.img_rec = d_img_rec; e.cam_rec = d_cam_rec;
-      e.img_intr_tmp = d_img_intr_tmp.p;
-      e.pose_free = d_pose_free.p; e.intr_free = d_intr_free.p; e.pt_free = d_pt_free.p;
-      e.poses = d_poses.p; e.intr = d_intr.p; e.points = d_points.p; e.gu = d_gu.p; e.norm_partial = d_norm_partial.p;
-      const int rows = e.gp + e.gc;
-      e.T.t[0] = ReduceTask{d_norm_partial.p, rows, 2, 1, nullptr, 0, d_scal.p + SC_GRAD_MAX};
-      e.T.t[1] = ReduceTask{d_norm_partial.p + 1, rows, 2, 0, nullptr, 0, d_scal.p + SC_XNORM2};
-      e.T.t[2] = ReduceTask{d_sweep_partial.p, eval_cost_rows(), 1, 0, d_prior_cost.p, num_priors, d_scal.p + SC_COST};
-      e.num_tasks = 3;
-      e.spec = spec;
-      launch_eval_small(st, e);
-    });
+    timed("eval_small", [&] { launch_eval_small(st, e); });
     evaluated = true; assembled = false;
     return;
   }
+  e.ride = pride;
+  prereduced = pride.n > 0;
   if (scales_ready && merge_on && !sharded() && NI <= 160) {
     // a medium problem on one rank: the evaluation's tail as two launches instead of four (k_eval_head / k_eval_tail, kernels.hip).
     // Measured: C2 (100 images) 24.0 -> 16.1 us; at C3 (500 images, two cameras of 250) the ONE work-group of the second launch
     // takes 34.5 us against 28.8 for the four launches - large problems keep those.
-    EvalSmallArgs e;
-    e.NI = NI; e.NC = NC; e.NP = NP; e.NPs = NPs; e.with_cams = any_intr_free ? 1 : 0; e.cam_part = rank == 0 ? 1 : 0;
-    state_norms_grid(NI, NC, NP, &e.gp, &e.gc);
-    if (eval_head_tail_fits(e.gc)) {
-      timed("eval_tail", [&] {
-        e.img_chunk_start = d_img_chunk_start.p; e.cam_partial = d_cam_partial.p;
-        e.prior_start = num_priors > 0 ? d_prior_start.p : nullptr; e.prior_res = d_prior_res.p; e.prior_jac = d_prior_jac.p;
-        e.cam_img_start = d_cam_img_start.p; e.cam_imgs = d_cam_imgs.p; e.img_rec = d_img_rec; e.cam_rec = d_cam_rec;
-        e.img_intr_tmp = d_img_intr_tmp.p;
-        e.pose_free = d_pose_free.p; e.intr_free = d_intr_free.p; e.pt_free = d_pt_free.p;
-        e.poses = d_poses.p; e.intr = d_intr.p; e.points = d_points.p; e.gu = d_gu.p; e.norm_partial = d_norm_partial.p;
-        const int rows = e.gp + e.gc;
-        e.T.t[0] = ReduceTask{d_norm_partial.p, rows, 2, 1, nullptr, 0, d_scal.p + SC_GRAD_MAX};
-        e.T.t[1] = ReduceTask{d_norm_partial.p + 1, rows, 2, 0, nullptr, 0, d_scal.p + SC_XNORM2};
-        e.T.t[2] = ReduceTask{d_sweep_partial.p, eval_cost_rows(), 1, 0, d_prior_cost.p, num_priors, d_scal.p + SC_COST};
-        e.num_tasks = 3;
-        e.spec = spec;
-        e.ride = pride;
-        launch_eval_head_tail(st, e);
-      });
-      prereduced = pride.n > 0;
-      evaluated = true; assembled = false;
-      return;
-    }
+    timed("eval_tail", [&] { launch_eval_head_tail(st, e); });
+    evaluated = true; assembled = false;
+    return;
   }
-  timed("camera_reduce", [&] {
-    launch_camera_reduce(st, NI, NC, d_img_chunk_start.p, d_cam_partial.p, num_priors > 0 ? d_prior_start.p : nullptr,
-                         d_prior_res.p, d_prior_jac.p, d_cam_img_start.p, d_cam_imgs.p, d_img_rec, d_cam_rec,
-                         d_img_intr_tmp.p, any_intr_free, spec, pride);
-  });
-  prereduced = pride.n > 0;
+  timed("camera_reduce", [&] { launch_camera_reduce(st, e); });
   allreduce(d_camsum.p, (long long)NI * kImgRec + (long long)NC * kCamRec, 0);
   if (!scales_ready) {
     timed("scales", [&] {
@@ -196,18 +188,8 @@ void mavba_session::evaluate_enqueue(double next_radius, const LmSpec& spec) {
     });
     scales_ready = true;
   }
-  int rows = 0;
-  timed("state_norms", [&] {
-    launch_state_norms(st, NI, NC, NP, NPs, rank == 0, d_pose_free.p, d_intr_free.p, d_pt_free.p, d_poses.p,
-                       d_intr.p, d_points.p, d_img_rec, d_cam_rec, d_gu.p, d_norm_partial.p, &rows, spec);
-  });
-  timed("reduce", [&] {
-    ReduceTasks T;
-    T.t[0] = ReduceTask{d_norm_partial.p, rows, 2, 1, nullptr, 0, d_scal.p + SC_GRAD_MAX};
-    T.t[1] = ReduceTask{d_norm_partial.p + 1, rows, 2, 0, nullptr, 0, d_scal.p + SC_XNORM2};
-    T.t[2] = ReduceTask{d_sweep_partial.p, eval_cost_rows(), 1, 0, d_prior_cost.p, num_priors, d_scal.p + SC_COST};
-    launch_reduce_tasks(st, T, 3, spec);
-  });
+  timed("state_norms", [&] { launch_state_norms(st, e); });
+  timed("reduce", [&] { launch_reduce_tasks(st, e.T, e.num_tasks, spec); });
   if (sharded()) allreduce(d_scal.p + SC_COST, SC_EVAL_COUNT, 2);  // the evaluation's two sums, then max|g| (never the candidate's slots)
   evaluated = true; assembled = false;
 }
@@ -257,7 +239,7 @@ void mavba_session::assemble(double r) {
     M_is_clean = true;
   }
   if (!(front_ok && fused_now())) timed("schur_clusters", [&] {
-    launch_schur_clusters(st, cl_shape, num_clusters, d_clusters.p, d_cl_tab.p, d_pt_start.p, d_q_start.p, d_obs_meta.p,
+    launch_schur_clusters(st, num_clusters, d_clusters.p, d_cl_tab.p, d_pt_start.p, d_q_start.p, d_obs_meta.p,
                           d_q_meta.p, d_pt_clustered.p, d_Epose.p, d_Eintr.p, d_h.p, NPs, d_part[0].p, d_part[1].p,
                           d_part[2].p);
   });
@@ -292,15 +274,8 @@ void mavba_session::solve_linear(double r) {
   decide_persistent();
   assemble(r);
   // (two timers: the forward factorisation - ONE kernel, k_chol_persist, on the persistent schedule - and the backward substitution)
-  CamUpdateArgs u;
-  const bool with_update = merge_small();
-  if (with_update) {
-    // (launch_update_cameras' arguments, as candidate_enqueue passes them)
-    u.NI = NI; u.NC = NC; u.cam_part = rank == 0 ? 1 : 0; u.radius = r; u.dmin = opt.min_lm_diagonal; u.dmax = opt.max_lm_diagonal;
-    u.scale_cam = d_scale_cam.p; u.img_rec = d_img_rec; u.cam_rec = d_cam_rec; u.poses = d_poses.p; u.intr = d_intr.p;
-    u.cand_poses = d_cposes.p; u.cand_intr = d_cintr.p; u.delta_cam = d_delta_cam.p;
-    u.partial3 = d_step_partial.p + 3 * (size_t)backsub_points_grid(NP); u.cand_camrec = d_ccamrec.p;
-  }
+  const CamUpdateArgs u = cam_update_args(r);
+  const bool with_update = merge_small();  // (a small system: the work-group that solves it applies the camera update as well)
   timed_split("chol_factor", "chol_backsolve", [&](hipEvent_t mid) {
     cameras_updated = dense_spd_solve_device(st, d_M.p, n_mat, d_ymat.p, d_scal.p + SC_FAIL, d_diag_ws.p, d_L.p, chol_struct, d_col_var.p, d_y.p,
                                              allow_persistent, mid, with_update ? &u : nullptr);
@@ -338,11 +313,7 @@ void mavba_session::candidate_enqueue(double r, ReduceTasks* tail, int* tail_cou
   // cameras first: the point back-substitution reads their step (delta_cam)
   const int rows = backsub_points_grid(NP), ugroups = update_cameras_groups(NI);
   if (!(cameras_updated && cameras_updated_r == r))  // (a small system: the work-group that solved it has done this already)
-    timed("update_cameras", [&] {
-      launch_update_cameras(st, NI, NC, rank == 0, r, dmin, dmax, d_y.p, d_scale_cam.p, d_img_rec, d_cam_rec,
-                            d_poses.p, d_intr.p, d_cposes.p, d_cintr.p, d_delta_cam.p, d_step_partial.p + 3 * (size_t)rows,
-                            d_ccamrec.p);  // (+ the candidate's camera records: no separate cam_prepare launch)
-    });
+    timed("update_cameras", [&] { launch_update_cameras(st, cam_update_args(r), d_y.p); });
   cameras_updated = false;
   // (round 4: for launch-bound problems the candidate's cost is summed by the back-substitution kernel itself - the observations
   // of a block's points are in its caches, the new points in its LDS -, one launch less: a 10-image window 2.30 -> 2.19 ms. At

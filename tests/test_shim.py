@@ -65,8 +65,11 @@ def mock_reference_fm():
     where they lie, only the Eigen vector types from the test double in tests/stubs: built by build(), see above."""
     if not os.path.exists(REFERENCE_FM_SHIM):
         pytest.skip("oracle/_ref/_shim_mock_reffm.so not built: build() compiles it only where the reference sources are present")
-    stale = [d for d in REFERENCE_FM_SHIM_DEPS if os.path.getmtime(d) > os.path.getmtime(REFERENCE_FM_SHIM)]
-    assert not stale, f"oracle/_ref/_shim_mock_reffm.so is older than {stale}: run build() again"
+    # (by content, like libmavba.so's stamp: a copied or re-extracted tree does not keep the order of the mtimes)
+    from mavmap_amd import build as b
+    stamp = REFERENCE_FM_SHIM + ".sha256"  # written by build() right behind the compilation
+    built_from = open(stamp).read().strip() if os.path.exists(stamp) else None
+    assert built_from == b.files_digest(REFERENCE_FM_SHIM_DEPS), "oracle/_ref/_shim_mock_reffm.so was built from other sources than the tree's: run build() again"
     return _mock_library(C.CDLL(REFERENCE_FM_SHIM))
 
 
