@@ -537,6 +537,7 @@ void intr_entries_on_device(const std::vector<unsigned char>& cam_active, std::v
   // one launch (k_eval_small) and the camera update inside the solve's launch (k_chol_small<true>). MAVBA_MERGE=0: off.
   bool merge_small() const;
   bool merge_on = true;             // MAVBA_MERGE (read in start())
+  long long sweep_ride_max_obs = -1;  // MAVBA_SWEEP_RIDE_MAX_OBS (read in start()): beyond local windows the camera sweep rides in the cluster launch up to this many observations; -1 (unset): no bound
   double pub_wait_seconds = 0.0;    // host time spent polling for the device's decision (MAVBA_SETUP_TIMING prints it)
   bool cameras_updated = false;     // the solve's launch has applied the camera update for ...
   double cameras_updated_r = 0.0;   // ... this radius

@@ -130,12 +130,17 @@ void mavba_session::evaluate_enqueue(double next_radius, const LmSpec& spec) {
   sweep_rode_along = false;
   if (front_ok) {
     // one pass: the evaluation's sums and (once the Jacobi scales exist and the next radius is known) the entries
-    // Beyond local windows, up to MAVBA_SWEEP_RIDE_MAX_OBS observations (default 1 000 000): the sweep's chunks fill the tail of the
-    // cluster launch - C2 4 095 -> 4 184 LM iterations/s, A/B/A/B, profiles/r06_ab_sweep_ride.txt. At C3 the merged launch is 19 us
-    // shorter than the two (1 285 -> 1 310 iter/s) and it stays OFF there by default: the cluster kernel is that configuration's
-    // dominant kernel and its roofline figures (time, flops, counters) are only meaningful for the kernel on its own; C5: no gain.
-    static const long long ride_max_obs = [] { const char* e = std::getenv("MAVBA_SWEEP_RIDE_MAX_OBS"); return e ? std::atoll(e) : 1000000ll; }();
-    const bool ride = scales_ready && num_sweep_chunks > 0 && (merge_small() || (merge_on && !sharded() && N <= ride_max_obs));
+    // Beyond local windows, on one rank, at every problem size: the sweep's chunks fill the tail of the cluster launch - one launch
+    // less per evaluation (C2 4 095 -> 4 184 LM iterations/s, profiles/r06_ab_sweep_ride.txt; C3: the merged launch is shorter than
+    // the two, profiles/ab_sweep_ride_all_sizes.txt). MAVBA_SWEEP_RIDE_MAX_OBS (read in start(), absent by default) is an upper
+    // bound on the observations of a problem that rides; 0 = local windows only.
+    // The profiled pass (opt.profile_kernels) of a problem of more than 1 000 000 observations keeps the two launches: the cluster
+    // kernel is such a problem's dominant kernel, and its entry in the kernel table, the roofline block and the committed counter
+    // passes describe that kernel on its own. The event-timed pass of a large problem therefore runs one launch more per
+    // evaluation than the timed loop (as with MAVBA_PARTIAL_RIDE below); results are bit-identical either way.
+    constexpr long long kProfiledRideMaxObs = 1000000;
+    const bool size_ok = (sweep_ride_max_obs < 0 || N <= sweep_ride_max_obs) && !(opt.profile_kernels && N > kProfiledRideMaxObs);
+    const bool ride = scales_ready && num_sweep_chunks > 0 && (merge_small() || (merge_on && !sharded() && size_ok));
     launch_front(next_radius, scales_ready && next_radius > 0.0, spec, ride ? &c : nullptr);
   } else {
     ensure_planes();
@@ -353,6 +358,7 @@ bool mavba_session::merge_small() const {
 void mavba_session::start() {
   { const char* e = std::getenv("MAVBA_MERGE"); merge_on = !e || std::atoi(e) != 0; }  // (read per solve: the tests compare both ways)
   { const char* e = std::getenv("MAVBA_SPECULATE"); speculate_on = !e || std::atoi(e) != 0; }  // (per solve, like MAVBA_MERGE)
+  { const char* e = std::getenv("MAVBA_SWEEP_RIDE_MAX_OBS"); sweep_ride_max_obs = e ? std::max(0ll, std::atoll(e)) : -1; }  // (per solve, like MAVBA_MERGE; unset: no bound)
   decide_persistent();
   evaluate();
   initial_cost = cost + fixed_cost;
