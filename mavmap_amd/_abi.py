@@ -1,4 +1,4 @@
-"""ctypes mirror of include/mavba.h (structs and constants only — no library here).
+"""ctypes mirror of include/mavba.h and include/mavba_triangulate.h (structs and constants only — no library here).
 
 Shared by the product wrapper (mavmap_amd.api) and, in tests/, by the oracle
 loader, so both sides of a parity test see byte-identical problem memory.
@@ -78,6 +78,22 @@ class CResult(C.Structure):
 class CPoseRefineItem(C.Structure):
     _fields_ = [("rvec", C.c_double * 3), ("tvec", C.c_double * 3), ("intrinsics", _dp), ("camera_model", C.c_int32),
                 ("uv", _dp), ("xyz", _dp), ("inlier_mask", _bp), ("n", C.c_int64)]
+
+
+# status bits of mavba_triangulate_pairs: the tests a correspondence FAILED
+TRI_REPROJ, TRI_ANGLE, TRI_DEPTH2, TRI_DEPTH1 = 1, 2, 4, 8
+# reject_bits of the reference's two call sites (src/sfm/sequential_mapper.cc:795-801, :341)
+TRI_REJECT_EXTEND = TRI_REPROJ | TRI_ANGLE | TRI_DEPTH2
+TRI_REJECT_INITIAL = TRI_DEPTH1
+
+
+class CTriPair(C.Structure):
+    _fields_ = [("rvec1", C.c_double * 3), ("tvec1", C.c_double * 3), ("rvec2", C.c_double * 3), ("tvec2", C.c_double * 3),
+                ("intrinsics1", _dp), ("intrinsics2", _dp), ("camera_model1", C.c_int32), ("camera_model2", C.c_int32),
+                ("uv1", _dp), ("uv2", _dp), ("n", C.c_int64), ("xyz_in", _dp), ("has_xyz", _bp),
+                ("max_reproj_error_px", C.c_double), ("min_angle_deg", C.c_double), ("reject_bits", C.c_uint32),
+                ("xyz", _dp), ("angle", _dp), ("reproj_error", _dp), ("depth", _dp), ("status", _ip), ("accepted", _ip),
+                ("num_accepted", C.c_int64), ("mean_folded_angle_deg", C.c_double), ("kernel_seconds", C.c_double)]
 
 
 class CSceneOptions(C.Structure):

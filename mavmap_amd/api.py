@@ -38,6 +38,9 @@ EXPORTED_SYMBOLS = [
     "mavba_debug_elimination_tree", "mavba_debug_radix_sort", "mavba_debug_lm_decide", "mavba_debug_chol_schedule",
     "mavba_debug_inproc_comms", "mavba_debug_upload_batch",
 ]
+# include/mavba_triangulate.h (a header of its own: mavba.h is what the drop-in translation unit is compiled against);
+# load() resolves them with their argument types, so a library without one does not load
+TRIANGULATE_SYMBOLS = ["mavba_triangulate_pairs"]
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
 
@@ -110,6 +113,8 @@ def load():
     L.mavba_rccl_unique_id.argtypes = [C.c_void_p]
     L.mavba_session_set_rccl.argtypes = [sp, C.c_void_p, C.c_int32, C.c_int32]
     L.mavba_pose_refine_batch.argtypes = [C.c_int32, C.POINTER(A.CPoseRefineItem), op, rp]
+    L.mavba_triangulate_pairs.argtypes = [C.c_int32, C.POINTER(A.CTriPair), C.c_int32]
+    L.mavba_triangulate_pairs.restype = C.c_int
     L.mavba_session_set_params.argtypes = [sp, dp, dp, dp]
     L.mavba_session_restart.argtypes = [sp]
     L.mavba_session_filter_points.argtypes = [sp, C.c_double, bp, bp, dp, C.POINTER(C.c_int64)]
@@ -285,6 +290,76 @@ def pose_refinement_batch(items, options=None, **kw):
         d = res[q].as_dict()
         out.append((float(np.sqrt(d["final_cost"] / d["num_residuals"])) if d["num_residuals"] else float("nan"), d))
     return out
+
+
+@dataclass
+class TriangulationResult:
+    """What mavba_triangulate_pairs returns for one image pair (arrays in the caller's order)."""
+    xyz: np.ndarray            # [n, 3]; xyz_in for a continued track
+    angle: np.ndarray          # [n] radians, unfolded
+    reproj_error: np.ndarray   # [n] image 2, normalised coordinates
+    depth: np.ndarray          # [n, 2] calc_depth in image 1, image 2
+    status: np.ndarray         # [n] int32, TRI_* bits of the failed tests
+    accepted: np.ndarray       # [num_accepted] int32, ascending
+    mean_folded_angle_deg: float
+    kernel_seconds: float
+
+    @property
+    def num_accepted(self):
+        return len(self.accepted)
+
+
+def _split_camera_params(camera_params):
+    cp = np.asarray(camera_params, float)
+    return A.as_f64(np.pad(cp[:-1], (0, 9 - (len(cp) - 1)))), int(cp[-1])
+
+
+def triangulate_pairs(items, tri_max_reproj_error=4.0, tri_min_angle=2.0, reject=A.TRI_REJECT_EXTEND, device=-1):
+    """Two-view triangulation with the mapper's acceptance tests, many image pairs in one launch
+    (mavba_triangulate_pairs; reference src/sfm/sequential_mapper.cc:755-810, initial pair :302-349).
+
+    `items`: list of dicts with rvec1, tvec1, rvec2, tvec2, camera_params1, camera_params2 (model code last, like
+    FeatureManager.camera_params), points2D1 / points2D2 [n, 2] in pixels and optionally points3D [n, 3] + has_point3D [n]
+    (the continued tracks). An item may override tri_max_reproj_error, tri_min_angle and reject. The defaults are the
+    reference's SequentialMapperOptions (4 px, 2 degrees) and its map-extension tests; its initial pair is
+    reject=TRI_REJECT_INITIAL plus mean_folded_angle_deg. Returns one TriangulationResult per item."""
+    count = len(items)
+    if count == 0:
+        return []
+    arr = (A.CTriPair * count)()
+    hold, outs = [], []
+    for q, it in enumerate(items):
+        intr1, model1 = _split_camera_params(it["camera_params1"])
+        intr2, model2 = _split_camera_params(it["camera_params2"])
+        uv1, uv2 = A.as_f64(it["points2D1"], (-1, 2)), A.as_f64(it["points2D2"], (-1, 2))
+        n = len(uv1)
+        if len(uv2) != n:
+            raise ValueError("points2D1 and points2D2 differ in length")
+        has = it.get("has_point3D")
+        xin = None
+        if has is not None:
+            has = np.ascontiguousarray(has, dtype=np.uint8).reshape(n)
+            xin = A.as_f64(it["points3D"], (n, 3))
+        hold.append((intr1, intr2, uv1, uv2, has, xin))
+        c = arr[q]
+        for k in range(3):
+            c.rvec1[k] = float(it["rvec1"][k]); c.tvec1[k] = float(it["tvec1"][k])
+            c.rvec2[k] = float(it["rvec2"][k]); c.tvec2[k] = float(it["tvec2"][k])
+        c.intrinsics1 = _d(intr1); c.intrinsics2 = _d(intr2); c.camera_model1 = model1; c.camera_model2 = model2
+        c.uv1 = _d(uv1); c.uv2 = _d(uv2); c.n = n
+        c.xyz_in = _d(xin); c.has_xyz = A.ptr(has, C.c_uint8)
+        c.max_reproj_error_px = float(it.get("tri_max_reproj_error", tri_max_reproj_error))
+        c.min_angle_deg = float(it.get("tri_min_angle", tri_min_angle))
+        c.reject_bits = int(it.get("reject", reject))
+        o = dict(xyz=np.zeros((n, 3)), angle=np.zeros(n), reproj_error=np.zeros(n), depth=np.zeros((n, 2)),
+                 status=np.zeros(n, np.int32), accepted=np.zeros(n, np.int32))
+        c.xyz = _d(o["xyz"]); c.angle = _d(o["angle"]); c.reproj_error = _d(o["reproj_error"]); c.depth = _d(o["depth"])
+        c.status = A.ptr(o["status"], C.c_int32); c.accepted = A.ptr(o["accepted"], C.c_int32)
+        outs.append(o)
+    _check(load().mavba_triangulate_pairs(count, arr, int(device)))
+    return [TriangulationResult(o["xyz"], o["angle"], o["reproj_error"], o["depth"], o["status"],
+                                o["accepted"][:int(arr[q].num_accepted)].copy(), float(arr[q].mean_folded_angle_deg),
+                                float(arr[q].kernel_seconds)) for q, o in enumerate(outs)]
 
 
 class Scene:

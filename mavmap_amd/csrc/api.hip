@@ -786,6 +786,17 @@ int mavba_pose_refine_batch(int32_t count, mavba_pose_refine_item* items, const 
   MAVBA_CATCH
 }
 
+// Two-view triangulation with the mapper's acceptance tests (triangulate.hip): replaces the host step of
+// src/sfm/sequential_mapper.cc:755-810 / :302-349 (image2world, triangulate_points, calc_tri_angles, calc_reproj_errors, calc_depth).
+int mavba_triangulate_pairs(int32_t count, mavba_tri_pair* items, int32_t device) {
+  if (count < 0 || (count > 0 && !items)) { g_last_error = "null argument"; return MAVBA_ERR_INVALID_ARGUMENT; }
+  if (count == 0) return MAVBA_OK;
+  MAVBA_TRY
+  triangulate_pairs(count, items, device);  // (arguments first, then the device: an invalid call says so on any machine)
+  return MAVBA_OK;
+  MAVBA_CATCH
+}
+
 int mavba_pose_refine(double rvec[3], double tvec[3], const double* intrinsics, int32_t camera_model,
                       const double* uv, const double* xyz, const uint8_t* inlier_mask, int64_t n,
                       const mavba_options* options, mavba_result* result) {

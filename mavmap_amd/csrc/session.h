@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/mavba.h"
+#include "../../include/mavba_triangulate.h"
 #include "ba_math.h"
 #include "internal.h"
 
@@ -94,6 +95,9 @@ int solve_multi_gpu(const mavba_problem* P, const mavba_options* options, mavba_
 
 // pose_refine.hip
 void pose_refine_batch(int count, mavba_pose_refine_item* items, const mavba_options& opt, mavba_result* results);
+
+// triangulate.hip
+void triangulate_pairs(int count, mavba_tri_pair* items, int device);
 
 // host_util.hip
 void rccl_unique_id(void* out128);
