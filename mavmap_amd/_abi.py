@@ -1,4 +1,4 @@
-"""ctypes mirror of include/mavba.h and include/mavba_triangulate.h (structs and constants only — no library here).
+"""ctypes mirror of include/mavba.h, include/mavba_triangulate.h and include/mavba_absolute_pose.h (structs and constants only — no library here).
 
 Shared by the product wrapper (mavmap_amd.api) and, in tests/, by the oracle
 loader, so both sides of a parity test see byte-identical problem memory.
@@ -94,6 +94,21 @@ class CTriPair(C.Structure):
                 ("max_reproj_error_px", C.c_double), ("min_angle_deg", C.c_double), ("reject_bits", C.c_uint32),
                 ("xyz", _dp), ("angle", _dp), ("reproj_error", _dp), ("depth", _dp), ("status", _ip), ("accepted", _ip),
                 ("num_accepted", C.c_int64), ("mean_folded_angle_deg", C.c_double), ("kernel_seconds", C.c_double)]
+
+
+# item status of mavba_absolute_pose_ransac (an item result, not a call error)
+ABSPOSE_OK, ABSPOSE_NO_CONSENSUS = 0, 1
+
+
+class CAbsPoseItem(C.Structure):
+    _fields_ = [("intrinsics", _dp), ("camera_model", C.c_int32), ("uv", _dp), ("xyz", _dp), ("n", C.c_int64),
+                ("max_reproj_error_px", C.c_double), ("max_trials", C.c_int32), ("stop_num_inliers", C.c_int64),
+                ("probability", C.c_double), ("samples", _ip), ("seed", C.c_uint64),
+                ("inlier_mask", _bp), ("trial_models", _dp), ("trial_num_inliers", _ip), ("trial_residual_sum", _dp),
+                ("trial_samples", _ip),
+                ("rvec", C.c_double * 3), ("tvec", C.c_double * 3), ("proj_matrix", C.c_double * 12),
+                ("num_inliers", C.c_int32), ("best_trial", C.c_int32), ("trials_used", C.c_int32), ("status", C.c_int32),
+                ("kernel_seconds", C.c_double)]
 
 
 class CSceneOptions(C.Structure):

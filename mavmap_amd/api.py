@@ -41,6 +41,8 @@ EXPORTED_SYMBOLS = [
 # include/mavba_triangulate.h (a header of its own: mavba.h is what the drop-in translation unit is compiled against);
 # load() resolves them with their argument types, so a library without one does not load
 TRIANGULATE_SYMBOLS = ["mavba_triangulate_pairs"]
+# include/mavba_absolute_pose.h, likewise
+ABSPOSE_SYMBOLS = ["mavba_absolute_pose_ransac"]
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
 
@@ -115,6 +117,8 @@ def load():
     L.mavba_pose_refine_batch.argtypes = [C.c_int32, C.POINTER(A.CPoseRefineItem), op, rp]
     L.mavba_triangulate_pairs.argtypes = [C.c_int32, C.POINTER(A.CTriPair), C.c_int32]
     L.mavba_triangulate_pairs.restype = C.c_int
+    L.mavba_absolute_pose_ransac.argtypes = [C.c_int32, C.POINTER(A.CAbsPoseItem), C.c_int32]
+    L.mavba_absolute_pose_ransac.restype = C.c_int
     L.mavba_session_set_params.argtypes = [sp, dp, dp, dp]
     L.mavba_session_restart.argtypes = [sp]
     L.mavba_session_filter_points.argtypes = [sp, C.c_double, bp, bp, dp, C.POINTER(C.c_int64)]
@@ -360,6 +364,89 @@ def triangulate_pairs(items, tri_max_reproj_error=4.0, tri_min_angle=2.0, reject
     return [TriangulationResult(o["xyz"], o["angle"], o["reproj_error"], o["depth"], o["status"],
                                 o["accepted"][:int(arr[q].num_accepted)].copy(), float(arr[q].mean_folded_angle_deg),
                                 float(arr[q].kernel_seconds)) for q, o in enumerate(outs)]
+
+
+@dataclass
+class AbsolutePoseResult:
+    """What mavba_absolute_pose_ransac returns for one image."""
+    status: int                     # ABSPOSE_OK / ABSPOSE_NO_CONSENSUS
+    rvec: np.ndarray                # [3] (NaN without consensus)
+    tvec: np.ndarray                # [3]
+    proj_matrix: np.ndarray         # [3, 4] = trial_models[best_trial]
+    num_inliers: int
+    best_trial: int
+    trials_used: int
+    inlier_mask: np.ndarray         # [n] uint8, the layout pose_refinement_batch takes
+    trial_models: np.ndarray        # [max_trials, 3, 4]; NaN for an invalid trial
+    trial_num_inliers: np.ndarray   # [max_trials] int32
+    trial_residual_sum: np.ndarray  # [max_trials]
+    trial_samples: np.ndarray       # [max_trials, 4] int32, ascending
+    kernel_seconds: float
+
+    @property
+    def ok(self):
+        return self.status == A.ABSPOSE_OK
+
+
+def absolute_pose_ransac(items, max_reproj_error=4.0, max_trials=500, stop_num_inliers=0, probability=0.99, seed=0, device=-1,
+                         trial_outputs=True):
+    """Absolute pose from 2D-3D matches, P3P inside RANSAC, many images in one launch (mavba_absolute_pose_ransac;
+    reference src/sfm/sequential_mapper.cc:621-659). The result of an item is that of the reference's RANSAC() run on
+    one thread with the same samples.
+
+    `items`: list of dicts with camera_params (model code last, like FeatureManager.camera_params), points2D [n, 2] in
+    pixels and points3D [n, 3]. An item may override max_reproj_error, max_trials, stop_num_inliers (absolute, <= 0:
+    none), probability and seed, and may supply samples [max_trials, 4]; otherwise the library draws them from `seed`.
+    trial_outputs=False leaves the per-trial arrays out (they come back empty). Returns one AbsolutePoseResult per item."""
+    count = len(items)
+    if count == 0:
+        return []
+    arr = (A.CAbsPoseItem * count)()
+    hold, outs = [], []
+    for q, it in enumerate(items):
+        intr, model = _split_camera_params(it["camera_params"])
+        uv, xyz = A.as_f64(it["points2D"], (-1, 2)), A.as_f64(it["points3D"], (-1, 3))
+        n = len(uv)
+        if len(xyz) != n:
+            raise ValueError("points2D and points3D differ in length")
+        mt = int(it.get("max_trials", max_trials))
+        smp = it.get("samples")
+        if smp is not None:
+            smp = np.ascontiguousarray(smp, dtype=np.int32).reshape(max(mt, 0), 4)
+        hold.append((intr, uv, xyz, smp))
+        c = arr[q]
+        c.intrinsics = _d(intr); c.camera_model = model; c.uv = _d(uv); c.xyz = _d(xyz); c.n = n
+        c.max_reproj_error_px = float(it.get("max_reproj_error", max_reproj_error))
+        c.max_trials = mt
+        c.stop_num_inliers = int(it.get("stop_num_inliers", stop_num_inliers))
+        c.probability = float(it.get("probability", probability))
+        c.samples = A.ptr(smp, C.c_int32); c.seed = int(it.get("seed", seed)) & 0xFFFFFFFFFFFFFFFF
+        k = max(mt, 0) if trial_outputs else 0
+        o = dict(inlier_mask=np.zeros(n, np.uint8), trial_models=np.zeros((k, 3, 4)), trial_num_inliers=np.zeros(k, np.int32),
+                 trial_residual_sum=np.zeros(k), trial_samples=np.zeros((k, 4), np.int32))
+        c.inlier_mask = A.ptr(o["inlier_mask"], C.c_uint8)
+        if trial_outputs:
+            c.trial_models = _d(o["trial_models"]); c.trial_num_inliers = A.ptr(o["trial_num_inliers"], C.c_int32)
+            c.trial_residual_sum = _d(o["trial_residual_sum"]); c.trial_samples = A.ptr(o["trial_samples"], C.c_int32)
+        outs.append(o)
+    _check(load().mavba_absolute_pose_ransac(count, arr, int(device)))
+    return [AbsolutePoseResult(int(arr[q].status), np.array(arr[q].rvec), np.array(arr[q].tvec), np.array(arr[q].proj_matrix).reshape(3, 4),
+                               int(arr[q].num_inliers), int(arr[q].best_trial), int(arr[q].trials_used), o["inlier_mask"], o["trial_models"],
+                               o["trial_num_inliers"], o["trial_residual_sum"], o["trial_samples"], float(arr[q].kernel_seconds))
+            for q, o in enumerate(outs)]
+
+
+def to_pose_refine_items(items, results):
+    """The argument of pose_refinement_batch for the images whose RANSAC found a consensus: the chain of
+    sequential_mapper.cc:621-732 is absolute_pose_ransac -> to_pose_refine_items -> pose_refinement_batch. Every dict also
+    carries `index`, the position of its image in `items` (images without consensus are left out)."""
+    out = []
+    for q, (it, r) in enumerate(zip(items, results)):
+        if r.status != A.ABSPOSE_OK:
+            continue
+        out.append(dict(index=q, rvec=np.array(r.rvec, float), tvec=np.array(r.tvec, float), camera_params=it["camera_params"],
+                        points2D=it["points2D"], points3D=it["points3D"], inlier_mask=np.ascontiguousarray(r.inlier_mask, np.uint8)))
+    return out
 
 
 class Scene:

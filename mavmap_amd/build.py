@@ -13,9 +13,9 @@ CSRC = os.path.join(ROOT, "csrc")
 LIBDIR = os.path.join(ROOT, "lib")
 LIB = os.path.join(LIBDIR, "libmavba.so")
 OBJDIR = os.path.join(LIBDIR, "obj")
-SOURCES = ["kernels.hip", "schur_rows.hip", "dense_chol.hip", "pose_refine.hip", "triangulate.hip", "host_util.hip", "session_build.hip", "session_lm.hip", "scene.hip", "multi_gpu.hip", "device_setup.hip", "api.hip"]
-HEADERS = ["ba_math.h", "tri_math.h", "dev_reduce.h", "internal.h", "session.h", "lm_decide.h", "lm_bodies.h", "sweep_body.h", "launch_dispatch.h", os.path.join("..", "..", "include", "mavba.h"),
-           os.path.join("..", "..", "include", "mavba_triangulate.h")]
+SOURCES = ["kernels.hip", "schur_rows.hip", "dense_chol.hip", "pose_refine.hip", "triangulate.hip", "absolute_pose.hip", "host_util.hip", "session_build.hip", "session_lm.hip", "scene.hip", "multi_gpu.hip", "device_setup.hip", "api.hip"]
+HEADERS = ["ba_math.h", "tri_math.h", "p3p_math.h", "dev_reduce.h", "internal.h", "session.h", "lm_decide.h", "lm_bodies.h", "sweep_body.h", "launch_dispatch.h", os.path.join("..", "..", "include", "mavba.h"),
+           os.path.join("..", "..", "include", "mavba_triangulate.h"), os.path.join("..", "..", "include", "mavba_absolute_pose.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wall",
          "-Wno-unused-result"]
 # Per-file additions. dense_chol.hip: matrix instructions with their accumulators in ordinary vector registers - the
@@ -75,6 +75,8 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=False):
+    if not force and is_current():  # built from exactly these sources and flags: the object files need not be there
+        return LIB
     os.makedirs(OBJDIR, exist_ok=True)
     hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
     hipcc = _hipcc()

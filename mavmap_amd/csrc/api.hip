@@ -797,6 +797,17 @@ int mavba_triangulate_pairs(int32_t count, mavba_tri_pair* items, int32_t device
   MAVBA_CATCH
 }
 
+// Absolute pose from 2D-3D matches, P3P inside RANSAC (absolute_pose.hip): replaces the host step of
+// src/sfm/sequential_mapper.cc:621-659 (image2world, RANSAC with the P3P estimator, rvec of the best model).
+int mavba_absolute_pose_ransac(int32_t count, mavba_abspose_item* items, int32_t device) {
+  if (count < 0 || (count > 0 && !items)) { g_last_error = "null argument"; return MAVBA_ERR_INVALID_ARGUMENT; }
+  if (count == 0) return MAVBA_OK;
+  MAVBA_TRY
+  absolute_pose_ransac(count, items, device);  // (arguments first, then the device: an invalid call says so on any machine)
+  return MAVBA_OK;
+  MAVBA_CATCH
+}
+
 int mavba_pose_refine(double rvec[3], double tvec[3], const double* intrinsics, int32_t camera_model,
                       const double* uv, const double* xyz, const uint8_t* inlier_mask, int64_t n,
                       const mavba_options* options, mavba_result* result) {

@@ -24,6 +24,7 @@
 
 #include "../../include/mavba.h"
 #include "../../include/mavba_triangulate.h"
+#include "../../include/mavba_absolute_pose.h"
 #include "ba_math.h"
 #include "internal.h"
 
@@ -98,6 +99,9 @@ void pose_refine_batch(int count, mavba_pose_refine_item* items, const mavba_opt
 
 // triangulate.hip
 void triangulate_pairs(int count, mavba_tri_pair* items, int device);
+
+// absolute_pose.hip
+void absolute_pose_ransac(int count, mavba_abspose_item* items, int device);
 
 // host_util.hip
 void rccl_unique_id(void* out128);
