@@ -43,6 +43,8 @@ EXPORTED_SYMBOLS = [
 TRIANGULATE_SYMBOLS = ["mavba_triangulate_pairs"]
 # include/mavba_absolute_pose.h, likewise
 ABSPOSE_SYMBOLS = ["mavba_absolute_pose_ransac"]
+# include/mavba_relative_pose.h, likewise
+RELPOSE_SYMBOLS = ["mavba_relative_pose_ransac"]
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
 
@@ -119,6 +121,8 @@ def load():
     L.mavba_triangulate_pairs.restype = C.c_int
     L.mavba_absolute_pose_ransac.argtypes = [C.c_int32, C.POINTER(A.CAbsPoseItem), C.c_int32]
     L.mavba_absolute_pose_ransac.restype = C.c_int
+    L.mavba_relative_pose_ransac.argtypes = [C.c_int32, C.POINTER(A.CRelPoseItem), C.c_int32]
+    L.mavba_relative_pose_ransac.restype = C.c_int
     L.mavba_session_set_params.argtypes = [sp, dp, dp, dp]
     L.mavba_session_restart.argtypes = [sp]
     L.mavba_session_filter_points.argtypes = [sp, C.c_double, bp, bp, dp, C.POINTER(C.c_int64)]
@@ -446,6 +450,110 @@ def to_pose_refine_items(items, results):
             continue
         out.append(dict(index=q, rvec=np.array(r.rvec, float), tvec=np.array(r.tvec, float), camera_params=it["camera_params"],
                         points2D=it["points2D"], points3D=it["points3D"], inlier_mask=np.ascontiguousarray(r.inlier_mask, np.uint8)))
+    return out
+
+
+@dataclass
+class RelativePoseResult:
+    """What mavba_relative_pose_ransac returns for one image pair."""
+    status: int                     # RELPOSE_OK / RELPOSE_NO_CONSENSUS
+    E: np.ndarray                   # [3, 3] = trial_models[best_trial, best_model] (NaN without consensus); x2^T E x1 = 0
+    R: np.ndarray                   # [3, 3]
+    tvec: np.ndarray                # [3]
+    rvec: np.ndarray                # [3]
+    cheirality_counts: np.ndarray   # [4] int32: (R1, t), (R2, t), (R1, -t), (R2, -t)
+    cheirality_best: int
+    forward_z: float                # inv_second_proj_matrix(2, 3)
+    num_inliers: int
+    best_trial: int
+    best_model: int
+    trials_used: int
+    inlier_mask: np.ndarray         # [n] uint8
+    trial_num_models: np.ndarray    # [max_trials] int32
+    trial_models: np.ndarray        # [max_trials, 10, 3, 3]; NaN beyond a trial's count
+    trial_z: np.ndarray             # [max_trials, 10] ascending
+    trial_num_inliers: np.ndarray   # [max_trials, 10] int32
+    trial_residual_sum: np.ndarray  # [max_trials, 10]
+    trial_samples: np.ndarray       # [max_trials, 5] int32, ascending
+    kernel_seconds: float
+
+    @property
+    def ok(self):
+        return self.status == A.RELPOSE_OK
+
+
+def relative_pose_ransac(items, max_reproj_error=4.0, max_trials=1000, stop_num_inliers=0, probability=0.99, seed=0, device=-1,
+                         trial_outputs=True):
+    """Relative pose of image pairs from 2D-2D matches: the five-point solver inside RANSAC, then (R, t) by the
+    cheirality test, many pairs in one launch (mavba_relative_pose_ransac; reference src/sfm/sequential_mapper.cc:174-216,
+    :269-299). The result of an item is the reference's RANSAC() on one thread with the same samples and each trial's
+    models taken in ascending z.
+
+    `items`: list of dicts with camera_params1 / camera_params2 (model code last, like FeatureManager.camera_params) and
+    points2D1 / points2D2 [n, 2] in pixels. An item may override max_reproj_error, max_trials, stop_num_inliers (absolute,
+    <= 0: none), probability and seed, and may supply samples [max_trials, 5]; otherwise the library draws them from
+    `seed`. trial_outputs=False leaves the per-trial arrays out (they come back empty). Returns one RelativePoseResult
+    per item."""
+    count = len(items)
+    if count == 0:
+        return []
+    arr = (A.CRelPoseItem * count)()
+    hold, outs = [], []
+    for q, it in enumerate(items):
+        intr1, model1 = _split_camera_params(it["camera_params1"])
+        intr2, model2 = _split_camera_params(it["camera_params2"])
+        uv1, uv2 = A.as_f64(it["points2D1"], (-1, 2)), A.as_f64(it["points2D2"], (-1, 2))
+        n = len(uv1)
+        if len(uv2) != n:
+            raise ValueError("points2D1 and points2D2 differ in length")
+        mt = int(it.get("max_trials", max_trials))
+        smp = it.get("samples")
+        if smp is not None:
+            smp = np.ascontiguousarray(smp, dtype=np.int32).reshape(max(mt, 0), 5)
+        hold.append((intr1, intr2, uv1, uv2, smp))
+        c = arr[q]
+        c.intrinsics1 = _d(intr1); c.intrinsics2 = _d(intr2); c.camera_model1 = model1; c.camera_model2 = model2
+        c.uv1 = _d(uv1); c.uv2 = _d(uv2); c.n = n
+        c.max_reproj_error_px = float(it.get("max_reproj_error", max_reproj_error))
+        c.max_trials = mt
+        c.stop_num_inliers = int(it.get("stop_num_inliers", stop_num_inliers))
+        c.probability = float(it.get("probability", probability))
+        c.samples = A.ptr(smp, C.c_int32); c.seed = int(it.get("seed", seed)) & 0xFFFFFFFFFFFFFFFF
+        k = max(mt, 0) if trial_outputs else 0
+        o = dict(inlier_mask=np.zeros(n, np.uint8), trial_num_models=np.zeros(k, np.int32), trial_models=np.zeros((k, 10, 3, 3)),
+                 trial_z=np.zeros((k, 10)), trial_num_inliers=np.zeros((k, 10), np.int32), trial_residual_sum=np.zeros((k, 10)),
+                 trial_samples=np.zeros((k, 5), np.int32))
+        c.inlier_mask = A.ptr(o["inlier_mask"], C.c_uint8)
+        if trial_outputs:
+            c.trial_num_models = A.ptr(o["trial_num_models"], C.c_int32); c.trial_models = _d(o["trial_models"]); c.trial_z = _d(o["trial_z"])
+            c.trial_num_inliers = A.ptr(o["trial_num_inliers"], C.c_int32); c.trial_residual_sum = _d(o["trial_residual_sum"])
+            c.trial_samples = A.ptr(o["trial_samples"], C.c_int32)
+        outs.append(o)
+    _check(load().mavba_relative_pose_ransac(count, arr, int(device)))
+    return [RelativePoseResult(int(arr[q].status), np.array(arr[q].E).reshape(3, 3), np.array(arr[q].R).reshape(3, 3), np.array(arr[q].tvec),
+                               np.array(arr[q].rvec), np.array(arr[q].cheirality_counts, np.int32), int(arr[q].cheirality_best),
+                               float(arr[q].forward_z), int(arr[q].num_inliers), int(arr[q].best_trial), int(arr[q].best_model),
+                               int(arr[q].trials_used), o["inlier_mask"], o["trial_num_models"], o["trial_models"], o["trial_z"],
+                               o["trial_num_inliers"], o["trial_residual_sum"], o["trial_samples"], float(arr[q].kernel_seconds))
+            for q, o in enumerate(outs)]
+
+
+def to_triangulate_pairs(items, results, tri_max_reproj_error=4.0, tri_min_angle=2.0):
+    """The argument of triangulate_pairs for the pairs whose RANSAC found a consensus and a pose: the chain of
+    sequential_mapper.cc:174-349 is relative_pose_ransac -> to_triangulate_pairs -> triangulate_pairs. The first image
+    has rvec = tvec = 0, the second the recovered pose; the correspondences are the inliers, in order;
+    reject = TRI_REJECT_INITIAL (depth in image 1) and mean_folded_angle_deg of the result is the mapper's angle test.
+    Every dict also carries `index`, the position of its pair in `items`, and `inliers`, the positions of its
+    correspondences in the pair's matches (pairs without consensus or without a pose are left out)."""
+    out = []
+    for q, (it, r) in enumerate(zip(items, results)):
+        if r.status != A.RELPOSE_OK or r.cheirality_best < 0:
+            continue
+        inl = np.flatnonzero(np.asarray(r.inlier_mask))
+        out.append(dict(index=q, inliers=inl, rvec1=np.zeros(3), tvec1=np.zeros(3), rvec2=np.array(r.rvec, float), tvec2=np.array(r.tvec, float),
+                        camera_params1=it["camera_params1"], camera_params2=it["camera_params2"],
+                        points2D1=A.as_f64(it["points2D1"], (-1, 2))[inl], points2D2=A.as_f64(it["points2D2"], (-1, 2))[inl],
+                        tri_max_reproj_error=tri_max_reproj_error, tri_min_angle=tri_min_angle, reject=A.TRI_REJECT_INITIAL))
     return out
 
 

@@ -808,6 +808,17 @@ int mavba_absolute_pose_ransac(int32_t count, mavba_abspose_item* items, int32_t
   MAVBA_CATCH
 }
 
+// Relative pose from 2D-2D matches, the five-point solver inside RANSAC and the recovery of (R, t) (relative_pose.hip):
+// replaces the host step of src/sfm/sequential_mapper.cc:174-216 and :269-299 for a candidate initial pair.
+int mavba_relative_pose_ransac(int32_t count, mavba_relpose_item* items, int32_t device) {
+  if (count < 0 || (count > 0 && !items)) { g_last_error = "null argument"; return MAVBA_ERR_INVALID_ARGUMENT; }
+  if (count == 0) return MAVBA_OK;
+  MAVBA_TRY
+  relative_pose_ransac(count, items, device);  // (arguments first, then the device: an invalid call says so on any machine)
+  return MAVBA_OK;
+  MAVBA_CATCH
+}
+
 int mavba_pose_refine(double rvec[3], double tvec[3], const double* intrinsics, int32_t camera_model,
                       const double* uv, const double* xyz, const uint8_t* inlier_mask, int64_t n,
                       const mavba_options* options, mavba_result* result) {

@@ -25,6 +25,7 @@
 #include "../../include/mavba.h"
 #include "../../include/mavba_triangulate.h"
 #include "../../include/mavba_absolute_pose.h"
+#include "../../include/mavba_relative_pose.h"
 #include "ba_math.h"
 #include "internal.h"
 
@@ -102,6 +103,9 @@ void triangulate_pairs(int count, mavba_tri_pair* items, int device);
 
 // absolute_pose.hip
 void absolute_pose_ransac(int count, mavba_abspose_item* items, int device);
+
+// relative_pose.hip
+void relative_pose_ransac(int count, mavba_relpose_item* items, int device);
 
 // host_util.hip
 void rccl_unique_id(void* out128);
