@@ -45,6 +45,8 @@ TRIANGULATE_SYMBOLS = ["mavba_triangulate_pairs"]
 ABSPOSE_SYMBOLS = ["mavba_absolute_pose_ransac"]
 # include/mavba_relative_pose.h, likewise
 RELPOSE_SYMBOLS = ["mavba_relative_pose_ransac"]
+# include/mavba_backsub_tiles.h, likewise
+BACKSUB_TILES_SYMBOLS = ["mavba_debug_backsub_tiles"]
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
 
@@ -130,6 +132,8 @@ def load():
     L.mavba_debug_elimination_tree.argtypes = [C.c_int32, C.c_int32, C.c_int64, ip, ip, C.c_int32, ip, ip, C.c_int32]
     L.mavba_debug_radix_sort.argtypes = [C.c_int32, C.POINTER(C.c_uint32), C.c_int32, ip, C.c_int32]
     L.mavba_debug_lm_decide.argtypes = [C.c_int32, dp, dp, dp, C.c_int32]
+    L.mavba_debug_backsub_tiles.argtypes = [C.c_int32, ip, ip, C.c_int32]
+    L.mavba_debug_backsub_tiles.restype = C.c_int
     i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
     L.mavba_debug_chol_schedule.argtypes = [C.c_int32, C.c_int32, i32p, i32p, i32p, C.c_int64, i32p, i32p, C.c_int32, dp,
                                             i32p, C.c_int64, i64p, i32p, C.c_int64, i64p, i32p]
@@ -827,6 +831,18 @@ def elimination_tree(num_images, num_cameras, pairs, max_depth=3):
     if n < 0:
         _check(n)
     return node[:num_images], parent[:n]
+
+
+def backsub_tiles(pt_start):
+    """The wave tiles of the point back-substitution for points with observations [pt_start[q], pt_start[q + 1]); no GPU
+    needed. Returns an [n, 4] array: first point, points, first observation, observations of every tile."""
+    pt_start = np.ascontiguousarray(pt_start, dtype=np.int32)
+    num_points = max(len(pt_start) - 1, 0)
+    out = np.zeros((max(num_points, 1), 4), np.int32)
+    n = load().mavba_debug_backsub_tiles(num_points, A.ptr(pt_start, C.c_int32), A.ptr(out, C.c_int32), num_points)
+    if n < 0:
+        _check(n)
+    return out[:n].copy()
 
 
 def radix_sort_order(keys, key_bytes=4, device=-1):

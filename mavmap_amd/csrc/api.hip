@@ -348,6 +348,21 @@ int mavba_session_eval_jacobian(mavba_session* s, double* cost, double* r, doubl
 
 int mavba_session_reduced_dim(mavba_session* s) { return s ? s->n_full : 0; }
 
+// Debug / test entry (no device needed): the wave tiles the session set-up builds for the point back-substitution.
+int mavba_debug_backsub_tiles(int32_t NP, const int32_t* pt_start, int32_t* tiles_out, int32_t cap) {
+  MAVBA_TRY
+  if (NP < 0 || !pt_start || cap < 0 || (cap > 0 && !tiles_out)) throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "bad argument");
+  for (int q = 0; q < NP; ++q)
+    if (pt_start[q + 1] < pt_start[q]) throw Failure(MAVBA_ERR_BAD_INDEX, "pt_start must not decrease");
+  const std::vector<BsTile> tiles = build_backsub_tiles(pt_start, NP);
+  if ((long long)tiles.size() > cap) throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "tiles_out too small");
+  for (size_t t = 0; t < tiles.size(); ++t) {
+    tiles_out[4 * t] = tiles[t].p0; tiles_out[4 * t + 1] = tiles[t].np; tiles_out[4 * t + 2] = tiles[t].o0; tiles_out[4 * t + 3] = tiles[t].no;
+  }
+  return (int)tiles.size();
+  MAVBA_CATCH
+}
+
 // Debug / test entry (no device needed): the elimination tree the session set-up would choose for an image graph given
 // as `npairs` coupled image pairs. node_of_image [NI] receives every image's tree node, node_parent [cap] the parents
 // (-1: root); returns the number of nodes (0: no dissection) or a negative error code.

@@ -307,6 +307,21 @@ void launch_backsub_points_jvp(hipStream_t st, int NP, int NPs, int NI, double r
                                const double* gu, const double* scale_pt, double* cand_points, double* delta_points,
                                double* partial /*[grid][3]*/, const double* cand_camrec = nullptr, const double* cand_intr = nullptr,
                                double* cost_partial = nullptr);
+// Wave tiles of the back-substitution (k_backsub_points_tiles): a run of consecutive points that one wave takes, one lane per
+// observation and one owner lane per point - at most 64 observations and at most 64 points; a point with more than 64
+// observations is a tile of its own (walked in chunks of 64). Built once at set-up from pt_start alone (no device, one serial
+// pass: the tiles do not depend on the host's threads); the filter mask changes no tile.
+struct BsTile { int p0, np, o0, no; };  // points [p0, p0 + np), their observations [o0, o0 + no)
+constexpr int kBsTileObs = 64, kBsTilePts = 64;
+std::vector<BsTile> build_backsub_tiles(const int* pt_start, int NP);
+int backsub_tiles_grid(int num_tiles);  // work-groups (= rows of partial / cost_partial) of the tile kernel: four tiles per trip
+// the same step by the tile kernel; cost_partial as above (null: the caller runs launch_cost_only behind it)
+void launch_backsub_points_tiles(hipStream_t st, int num_tiles, const BsTile* tiles, int NPs, int NI, double radius, double dmin,
+                                 double dmax, const SweepArgs& a, const int* pt_start, const double* delta_cam,
+                                 const unsigned char* pt_free, const double* Gi, const double* h, const double* Cu,
+                                 const double* gu, const double* scale_pt, double* cand_points, double* delta_points,
+                                 double* partial /*[grid][3]*/, const double* cand_camrec, const double* cand_intr,
+                                 double* cost_partial);
 // Camera columns: step = -y, delta = s * step, candidate parameters and (cand_camrec != null) their camera records.
 // mavba_session::cam_update_args fills one per radius; the reduced solve of a small system applies it in its own launch.
 struct CamUpdateArgs {

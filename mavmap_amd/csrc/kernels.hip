@@ -1795,6 +1795,227 @@ void launch_backsub_points_jvp(hipStream_t st, int NP, int NPs, int NI, double r
                      cost_partial);
 }
 
+// The same step on WAVE TILES (BsTile, internal.h): one wave per tile, the four waves of a work-group independent of each other.
+// k_backsub_points_packed spends its time between two work-group barriers per block with ~22 of 256 lanes summing, and keeps the
+// owner lanes' 21 doubles of point data live across the per-observation arithmetic. Here lane l takes observation l of its wave's
+// tile, the three values go to the WAVE's slice of LDS, lane j < np adds point j's observations in observation order (the same
+// sequence of additions as the block kernel: per-point results are bit-identical) and only then requests its point's data; the
+// candidate point goes back through the wave's slice and every lane - still holding its observation - evaluates the candidate's
+// residual. LDS traffic is ordered inside the wave only (wave_lds_sync); the one barrier of the tile loop's work-group is the
+// staging of the camera tables in front of it, the others belong to the four sums at the end. No flags, no atomics: the rows of
+// partial / cost_partial are sums in a fixed order.
+// Work-group b takes tiles 4 b + w (w = its wave), then strides by 4 x grid: neighbouring work-groups walk neighbouring points
+// (see the block kernel). The next tile's record and observations are requested one tile ahead.
+// Registers: 163 VGPRs = 3 waves per SIMD, no scratch (the block kernel: 209 = 2 waves). obs_backsub_term with its 36 doubles of
+// input takes 142 on its own, so the 128 of 4 waves per SIMD are out of reach without spills; the lanes' four running sums
+// live in LDS slots because 8 more registers across the arithmetic cost the third wave. Requesting the next tile's gathers one
+// tile ahead as well (200 VGPRs, 2 waves) measured slower: 88 against 75 us at C3 (profiles/ab_backsub_tiles.txt).
+__device__ __forceinline__ void wave_lds_sync() {  // (as in dense_chol.hip: orders the wave's own LDS traffic, no s_barrier)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <bool COST>
+__global__ void __launch_bounds__(256) k_backsub_points_tiles(
+    int num_tiles, const BsTile* __restrict__ tiles, int NPs, int NI, int NC, int N, double radius, double dmin, double dmax,
+    double loss_b, double loss_inv_b, const int* __restrict__ pt_start, const int* __restrict__ obs_img,
+    const int* __restrict__ obs_pt, const double2* __restrict__ uv, const int* __restrict__ img_cam,
+    const int* __restrict__ cam_model, const double* __restrict__ camrec, const double* __restrict__ intr,
+    const double* __restrict__ delta_cam, const unsigned char* __restrict__ pt_free, const double* __restrict__ Gi,
+    const double* __restrict__ h, const double* __restrict__ Cu, const double* __restrict__ gu,
+    const double* __restrict__ scale_pt, const double* __restrict__ points, double* __restrict__ cand_points,
+    double* __restrict__ delta_points, double* __restrict__ partial, const double* __restrict__ cand_camrec,
+    const double* __restrict__ cand_intr, const unsigned char* __restrict__ pt_active, double* __restrict__ cost_partial) {
+  __shared__ double s_t[4][3][kBsTileObs];    // per wave: the observations' three values
+  __shared__ double s_new[4][3][kBsTilePts];  // per wave: the tile's candidate points
+  __shared__ double s_red[4];
+  __shared__ double s_acc[4][256];  // the lanes' four running sums (kept out of the registers: they would be live across the arithmetic)
+  __shared__ double s_kin[kBsCamsLds][9], s_dk[kBsCamsLds][9], s_ckin[kBsCamsLds][9];
+  __shared__ int s_model[kBsCamsLds];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool cams_lds = NC <= kBsCamsLds;
+  const int stride = 4 * (int)gridDim.x;
+  s_acc[0][tid] = 0.0; s_acc[1][tid] = 0.0; s_acc[2][tid] = 0.0; s_acc[3][tid] = 0.0;  // (every lane reads and writes its own slots only)
+  struct Obs { int pt, im; double2 m; };
+  auto load_obs = [&](int o) {
+    Obs r{0, 0, make_double2(0.0, 0.0)};
+    if (N <= 0) return r;
+    const int oc = min(o, N - 1);  // (a lane beyond the tile reads the last observation and drops the result)
+    r.pt = obs_pt[oc]; r.im = obs_img[oc]; r.m = uv[oc];
+    return r;
+  };
+  auto load_tile = [&](int t) {
+    const int4 v = *reinterpret_cast<const int4*>(tiles + t);
+    return BsTile{v.x, v.y, v.z, v.w};
+  };
+  // one observation's three values (zero for a lane beyond the chunk or a point that is not free)
+  auto obs_term = [&](const Obs& q, bool valid, double (&t)[3]) {
+    t[0] = t[1] = t[2] = 0.0;
+    if (!valid || !pt_free[q.pt]) return;
+    const int cam = img_cam[q.im];
+    const double X[3] = {points[3 * (size_t)q.pt], points[3 * (size_t)q.pt + 1], points[3 * (size_t)q.pt + 2]};
+    double rec[9], kin[9], dc[6], dk[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) rec[k] = camrec[9 * q.im + k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) dc[k] = delta_cam[6 * q.im + k];
+    int model;
+    if (cams_lds) {
+      model = s_model[cam];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) { kin[k] = s_kin[cam][k]; dk[k] = s_dk[cam][k]; }
+    } else {
+      model = cam_model[cam];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) { kin[k] = intr[9 * cam + k]; dk[k] = delta_cam[6 * NI + 9 * cam + k]; }
+    }
+    double r[2], tt[3];
+    obs_backsub_term(model, rec, kin, X, q.m.x, q.m.y, dc, dk, r, tt);
+    double w, half_rho;
+    cauchy_weight(r[0] * r[0] + r[1] * r[1], loss_b, loss_inv_b, w, half_rho);
+    const double w2 = w * w;
+    t[0] = w2 * tt[0]; t[1] = w2 * tt[1]; t[2] = w2 * tt[2];
+  };
+  // this tile's record and observations, the next tile's record: requested one / two tiles ahead
+  int t = 4 * (int)blockIdx.x + wv;
+  BsTile T{0, 0, 0, 0}, Tn{0, 0, 0, 0};
+  Obs cur{0, 0, make_double2(0.0, 0.0)};
+  if (t < num_tiles) {
+    T = load_tile(t);
+    if (t + stride < num_tiles) Tn = load_tile(t + stride);
+    cur = load_obs(T.o0 + lane);
+  }
+  if (cams_lds) {  // (behind the first requests: they travel while the tables are staged)
+    for (int e = tid; e < 9 * NC; e += 256) {
+      s_kin[e / 9][e % 9] = intr[e]; s_dk[e / 9][e % 9] = delta_cam[6 * NI + e];
+      if constexpr (COST) s_ckin[e / 9][e % 9] = cand_intr[e];
+    }
+    for (int c = tid; c < NC; c += 256) s_model[c] = cam_model[c];
+    __syncthreads();
+  }
+  for (; t < num_tiles; t += stride) {
+    Obs nxt = cur;
+    BsTile Tnn{0, 0, 0, 0};
+    if (t + stride < num_tiles) {
+      nxt = load_obs(Tn.o0 + lane);
+      if (t + 2 * stride < num_tiles) Tnn = load_tile(t + 2 * stride);
+    }
+    const int p = T.p0 + lane;
+    const bool owner = lane < T.np;
+    int mb = 0, me = 0;  // the owner's observations, relative to the tile's first
+    if (owner) { mb = pt_start[p] - T.o0; me = pt_start[p + 1] - T.o0; }
+    double Ts[3] = {0.0, 0.0, 0.0};
+    for (int base = 0; base < T.no; base += kBsTileObs) {  // (more than one trip: a point of more than 64 observations, owner = lane 0)
+      const Obs q = base == 0 ? cur : load_obs(T.o0 + base + lane);
+      double tt[3];
+      obs_term(q, base + lane < T.no, tt);
+      s_t[wv][0][lane] = tt[0]; s_t[wv][1][lane] = tt[1]; s_t[wv][2][lane] = tt[2];
+      wave_lds_sync();
+      if (owner) {
+        const int b = max(mb, base), e = min(me, base + kBsTileObs);
+        for (int i = b; i < e; ++i) { Ts[0] += s_t[wv][0][i - base]; Ts[1] += s_t[wv][1][i - base]; Ts[2] += s_t[wv][2][i - base]; }
+      }
+      wave_lds_sync();  // (the next chunk rewrites the slice)
+    }
+    if (owner) {
+      // the point's data: requested here, behind the arithmetic, not held across it
+      const bool fr = pt_free[p] != 0;
+      double a_step = 0.0, a_model = 0.0, a_x2 = 0.0;
+      double d[3] = {0, 0, 0}, Xo[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) Xo[k] = points[3 * (size_t)p + k];
+      if (fr) {
+        const int dg[3] = {0, 3, 5};
+        double G[6], sp[3], hh[3], cu[3], gg[3];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) G[k] = Gi[k * NPs + p];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { sp[k] = scale_pt[k * NPs + p]; hh[k] = h[k * NPs + p]; cu[k] = Cu[dg[k] * NPs + p]; gg[k] = gu[k * NPs + p]; }
+        const double q0 = -sp[0] * Ts[0], q1 = -sp[1] * Ts[1], q2 = -sp[2] * Ts[2];
+        const double z[3] = {q0 * G[0], q0 * G[1] + q1 * G[2], q0 * G[3] + q1 * G[4] + q2 * G[5]};
+        const double tt[3] = {hh[0] - z[0], hh[1] - z[1], hh[2] - z[2]};
+        double yp[3];
+        git_mul(G, tt, yp);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double s = sp[k];
+          const double D2 = clampd(s * s * cu[k], dmin, dmax) / radius;
+          const double gs = s * gg[k];
+          a_model += 0.5 * yp[k] * (gs + D2 * yp[k]);
+          d[k] = -yp[k] * s;
+          a_step += d[k] * d[k];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double xn = Xo[k] + d[k];
+        cand_points[3 * (size_t)p + k] = xn;
+        delta_points[3 * (size_t)p + k] = d[k];
+        if (fr) a_x2 += xn * xn;
+        if constexpr (COST) s_new[wv][k][lane] = xn;
+      }
+      if (fr) { s_acc[0][tid] += a_step; s_acc[1][tid] += a_model; s_acc[2][tid] += a_x2; }
+    }
+    // ---- the candidate's cost over the tile's observations (what k_cost_only does in a launch of its own): the lane still
+    // holds its observation, the candidate point comes from the wave's slice, the candidate cameras from memory / LDS ----
+    if constexpr (COST) {
+      wave_lds_sync();
+      for (int base = 0; base < T.no; base += kBsTileObs) {
+        const Obs q = T.no <= kBsTileObs ? cur : load_obs(T.o0 + base + lane);  // (a chunked point re-reads its chunks)
+        if (base + lane < T.no) {
+          const int cam = img_cam[q.im];
+          double rec[9], kin[9], r[2];
+#pragma unroll
+          for (int k = 0; k < 9; ++k) rec[k] = cand_camrec[9 * q.im + k];
+          int model;
+          if (cams_lds) {
+            model = s_model[cam];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) kin[k] = s_ckin[cam][k];
+          } else {
+            model = cam_model[cam];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) kin[k] = cand_intr[9 * cam + k];
+          }
+          const int j = q.pt - T.p0;
+          const double Xn[3] = {s_new[wv][0][j], s_new[wv][1][j], s_new[wv][2][j]};
+          obs_residual(model, rec, kin, Xn, q.m.x, q.m.y, r);
+          double w, half_rho;
+          cauchy_weight(r[0] * r[0] + r[1] * r[1], loss_b, loss_inv_b, w, half_rho);
+          if (pt_active && !pt_active[q.pt]) half_rho = 0.0;  // filtered point: no residual block
+          s_acc[3][tid] += half_rho;
+        }
+      }
+      wave_lds_sync();  // (the next tile rewrites the slice)
+    }
+    T = Tn; Tn = Tnn; cur = nxt;
+  }
+  const double s0 = block_sum_256(s_acc[0][tid], s_red);
+  const double s1 = block_sum_256(s_acc[1][tid], s_red);
+  const double s2 = block_sum_256(s_acc[2][tid], s_red);
+  if (tid == 0) { partial[3 * blockIdx.x] = s0; partial[3 * blockIdx.x + 1] = s1; partial[3 * blockIdx.x + 2] = s2; }
+  if constexpr (COST) {
+    const double s3 = block_sum_256(s_acc[3][tid], s_red);
+    if (tid == 0) cost_partial[blockIdx.x] = s3;
+  }
+}
+// (at most 768 work-groups: 163 VGPRs = 3 waves per SIMD = 3 work-groups on each of 256 CUs - every work-group resident from the
+// start, none left for a second, thinly occupied round)
+int backsub_tiles_grid(int num_tiles) { return std::max(1, std::min(768, (num_tiles + 3) / 4)); }
+void launch_backsub_points_tiles(hipStream_t st, int num_tiles, const BsTile* tiles, int NPs, int NI, double radius, double dmin,
+                                 double dmax, const SweepArgs& a, const int* pt_start, const double* delta_cam,
+                                 const unsigned char* pt_free, const double* Gi, const double* h, const double* Cu,
+                                 const double* gu, const double* scale_pt, double* cand_points, double* delta_points,
+                                 double* partial, const double* cand_camrec, const double* cand_intr, double* cost_partial) {
+  with_bool(cost_partial != nullptr, [&](auto cost) {
+    hipLaunchKernelGGL((k_backsub_points_tiles<decltype(cost)::value>), dim3(backsub_tiles_grid(num_tiles)), dim3(256), 0, st, num_tiles,
+                       tiles, NPs, NI, a.NC, a.N, radius, dmin, dmax, a.loss_b, a.loss_inv_b, pt_start, a.obs_img, a.obs_pt, a.uv, a.img_cam,
+                       a.cam_model, a.camrec, a.intr, delta_cam, pt_free, Gi, h, Cu, gu, scale_pt, a.points, cand_points, delta_points,
+                       partial, cand_camrec, cand_intr, a.pt_active, cost_partial);
+  });
+}
+
 // Camera columns: step = -y, delta = s * step, candidate parameters (update_cameras_body, lm_bodies.h: work-group b takes
 // 42 images - one work-group looping over all 6 NI + 9 NC parameters took 22 us at C3).
 int update_cameras_groups(int NI) { return std::max(1, (NI + kUpdImagesPerGroup - 1) / kUpdImagesPerGroup); }

@@ -24,6 +24,7 @@
 
 #include "../../include/mavba.h"
 #include "../../include/mavba_triangulate.h"
+#include "../../include/mavba_backsub_tiles.h"
 #include "../../include/mavba_absolute_pose.h"
 #include "../../include/mavba_relative_pose.h"
 #include "ba_math.h"
@@ -317,6 +318,15 @@ struct mavba_session {
   double front_radius = 0.0;
   bool fail_slot_clean = false; // SC_FAIL was cleared (with SC_FAIL_FRONT, by the front end) and no solve has run since
   bool planes_ready = false;    // the Jacobian planes exist (probe path / plane kernels only)
+  // wave tiles of the back-substitution (k_backsub_points_tiles; built in build() from h_pt_start, never rebuilt)
+  DevBuf<BsTile> d_bs_tiles;
+  int num_bs_tiles = 0;
+  int backsub_blocks = -1;  // MAVBA_BACKSUB_BLOCKS (read per solve and per linear_step): 1 = k_backsub_points_packed everywhere, 0 = the tile kernel everywhere, -1 (unset) = the default below
+  void read_backsub_switch();
+  // The back-substitution's route and its grid (= its rows in d_step_partial / d_sweep_partial): every user asks here. Local
+  // windows keep the block kernel by default (see candidate_enqueue).
+  bool backsub_on_tiles() const { return backsub_blocks < 0 ? !small_window() : backsub_blocks == 0; }  // (not merge_small(): the route must not follow MAVBA_MERGE, whose two settings are compared bit for bit)
+  int backsub_rows() const { return backsub_on_tiles() ? backsub_tiles_grid(num_bs_tiles) : backsub_points_grid(NP); }
   DevBuf<SweepChunk> d_sweep_chunks;
   int num_sweep_chunks = 0;
   DevBuf<unsigned char> d_pose_free, d_intr_free, d_pt_free;
@@ -548,6 +558,7 @@ void intr_entries_on_device(const std::vector<unsigned char>& cam_active, std::v
   // Launch merging for problems whose reduced system one work-group solves (a local window): the evaluation's reductions in
   // one launch (k_eval_small) and the camera update inside the solve's launch (k_chol_small<true>). MAVBA_MERGE=0: off.
   bool merge_small() const;
+  bool small_window() const;  // the size test of merge_small() alone: a problem whose reduced system one work-group solves
   bool merge_on = true;             // MAVBA_MERGE (read in start())
   long long sweep_ride_max_obs = -1;  // MAVBA_SWEEP_RIDE_MAX_OBS (read in start()): beyond local windows the camera sweep rides in the cluster launch up to this many observations; -1 (unset): no bound
   double pub_wait_seconds = 0.0;    // host time spent polling for the device's decision (MAVBA_SETUP_TIMING prints it)

@@ -448,6 +448,11 @@ void mavba_session::build(const mavba_problem* P, const DeviceRaw* raw) {
   d_cam_img_start.upload(cam_img_start, st); d_cam_imgs.upload(cam_imgs, st);
   d_prior_img.upload(prior_img, st); d_prior_start.upload(prior_start, st); d_prior_R0.upload(prior_R0, st);
   d_pt_count.upload(h_pt_count_all, st);
+  {
+    const std::vector<BsTile> bs_tiles = build_backsub_tiles(h_pt_start.data(), NP);
+    num_bs_tiles = (int)bs_tiles.size();
+    d_bs_tiles.upload(bs_tiles, st);
+  }
   if (!device_order) { d_pt_orig.upload(h_pt_orig, st); d_points0.upload(h_points0, st); }
   d_pts_out.alloc((size_t)std::max(NP, 1) * 3);
   d_poses0.upload(h_poses0, st); d_intr0.upload(h_intr0, st);
@@ -1570,6 +1575,23 @@ void mavba_session::build_tiles(const std::vector<int>& q_start, int first, DevB
   count = (int)tiles.size();
   out.upload(tiles, st);
 }
+
+// Wave tiles of the back-substitution (BsTile, internal.h): greedy runs of whole consecutive points, one serial pass. Host only;
+// exported for tests as mavba_debug_backsub_tiles.
+namespace mavba {
+std::vector<BsTile> build_backsub_tiles(const int* pt_start, int NP) {
+  std::vector<BsTile> tiles;
+  int p = 0;
+  while (p < NP) {
+    const int p0 = p, o0 = pt_start[p];
+    if (pt_start[p + 1] - o0 > kBsTileObs) { ++p; }  // a long point: a tile of its own
+    else
+      while (p < NP && p - p0 < kBsTilePts && pt_start[p + 1] - o0 <= kBsTileObs) ++p;  // (a long point ends the run: its end is beyond o0 + 64)
+    tiles.push_back(BsTile{p0, p - p0, o0, pt_start[p] - o0});
+  }
+  return tiles;
+}
+}  // namespace mavba
 
 void mavba_session::reset_state() {
   front_valid = false;

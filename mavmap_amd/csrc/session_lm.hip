@@ -112,7 +112,7 @@ CamUpdateArgs mavba_session::cam_update_args(double r) {
   u.NI = NI; u.NC = NC; u.cam_part = rank == 0 ? 1 : 0; u.radius = r; u.dmin = opt.min_lm_diagonal; u.dmax = opt.max_lm_diagonal;
   u.scale_cam = d_scale_cam.p; u.img_rec = d_img_rec; u.cam_rec = d_cam_rec; u.poses = d_poses.p; u.intr = d_intr.p;
   u.cand_poses = d_cposes.p; u.cand_intr = d_cintr.p; u.delta_cam = d_delta_cam.p;
-  u.partial3 = d_step_partial.p + 3 * (size_t)backsub_points_grid(NP); u.cand_camrec = d_ccamrec.p;
+  u.partial3 = d_step_partial.p + 3 * (size_t)backsub_rows(); u.cand_camrec = d_ccamrec.p;
   return u;
 }
 
@@ -292,10 +292,16 @@ void mavba_session::solve_linear(double r) {
   if (!(allow_persistent && chol_struct.persist_ok) || sharded()) M_is_clean = false;
 }
 
+void mavba_session::read_backsub_switch() {
+  const char* e = std::getenv("MAVBA_BACKSUB_BLOCKS");
+  backsub_blocks = e ? (std::atoi(e) != 0 ? 1 : 0) : -1;
+}
+
 // One LM linear step: reduced solve + candidate. The persistent factorisation bounds every wait; should a launch ever
 // give up (its work-groups were not all resident: another persistent launch on the device, CU masking), the solve is
 // repeated once with the launch-per-panel schedule and the session stays on that schedule.
 void mavba_session::linear_step(double r, double* h) {
+  read_backsub_switch();  // (per call: the tests compare the two routes on one session's inputs)
   solve_linear(r);
   candidate(r, h);
   if (h[SC_FAIL] >= 1e29 && allow_persistent) {
@@ -316,20 +322,32 @@ void mavba_session::candidate(double r, double* h) {
 void mavba_session::candidate_enqueue(double r, ReduceTasks* tail, int* tail_count) {
   const double dmin = opt.min_lm_diagonal, dmax = opt.max_lm_diagonal;
   // cameras first: the point back-substitution reads their step (delta_cam)
-  const int rows = backsub_points_grid(NP), ugroups = update_cameras_groups(NI);
+  const bool tiles = backsub_on_tiles();
+  const int rows = backsub_rows(), ugroups = update_cameras_groups(NI);
   if (!(cameras_updated && cameras_updated_r == r))  // (a small system: the work-group that solved it has done this already)
     timed("update_cameras", [&] { launch_update_cameras(st, cam_update_args(r), d_y.p); });
   cameras_updated = false;
+  // The tile kernel (k_backsub_points_tiles, one wave per run of points with at most 64 observations) sums the candidate's cost
+  // itself at every size: its lanes still hold their observations when the candidate point exists - no second pass over the
+  // observations, no k_cost_only launch (profiles/ab_backsub_tiles.txt). Local windows keep the block kernel unless
+  // MAVBA_BACKSUB_BLOCKS=0 asks for the tiles; MAVBA_BACKSUB_BLOCKS=1 is the block kernel everywhere, with its own rule:
   // (round 4: for launch-bound problems the candidate's cost is summed by the back-substitution kernel itself - the observations
   // of a block's points are in its caches, the new points in its LDS -, one launch less: a 10-image window 2.30 -> 2.19 ms. At
   // C3 / C5 the streaming k_cost_only is the faster way to do that pass (0.091 + 0.023 against 0.123 ms), so large problems keep
-  // it. MAVBA_COST_FUSE_MAX_OBS moves the switch, 0 = never fuse)
-  static const long long fuse_max_obs = [] { const char* e = std::getenv("MAVBA_COST_FUSE_MAX_OBS"); return e ? std::atoll(e) : 500000ll; }();  // (round 6: 200 000 -> 500 000 - C2, 300 000 observations: 4 058 -> 4 109 iter/s fused, A/B/A/B)
-  const bool cost_separate = (long long)N > fuse_max_obs;
+  // it. MAVBA_COST_FUSE_MAX_OBS moves the switch, 0 = never fuse; when it is set, the tile kernel obeys it too - an A/B of the fold)
+  static const long long fuse_env = [] { const char* e = std::getenv("MAVBA_COST_FUSE_MAX_OBS"); return e ? std::atoll(e) : -1ll; }();
+  const long long fuse_max_obs = fuse_env >= 0 ? fuse_env : 500000ll;  // (round 6: 200 000 -> 500 000 - C2, 300 000 observations: 4 058 -> 4 109 iter/s fused, A/B/A/B)
+  const bool cost_separate = tiles && fuse_env < 0 ? false : (long long)N > fuse_max_obs;
+  double* cost_rows = cost_separate ? nullptr : d_sweep_partial.p;
   timed("backsub_points", [&] {
-    launch_backsub_points_jvp(st, NP, NPs, NI, r, dmin, dmax, sweep_args(d_camrec.p, d_intr.p, d_points.p), d_pt_start.p,
-                              d_delta_cam.p, d_pt_free.p, d_Gi.p, d_h.p, d_Cu.p, d_gu.p, d_scale_pt.p, d_cpoints.p,
-                              d_delta_pts.p, d_step_partial.p, d_ccamrec.p, d_cintr.p, cost_separate ? nullptr : d_sweep_partial.p);
+    if (tiles)
+      launch_backsub_points_tiles(st, num_bs_tiles, d_bs_tiles.p, NPs, NI, r, dmin, dmax, sweep_args(d_camrec.p, d_intr.p, d_points.p),
+                                  d_pt_start.p, d_delta_cam.p, d_pt_free.p, d_Gi.p, d_h.p, d_Cu.p, d_gu.p, d_scale_pt.p, d_cpoints.p,
+                                  d_delta_pts.p, d_step_partial.p, d_ccamrec.p, d_cintr.p, cost_rows);
+    else
+      launch_backsub_points_jvp(st, NP, NPs, NI, r, dmin, dmax, sweep_args(d_camrec.p, d_intr.p, d_points.p), d_pt_start.p,
+                                d_delta_cam.p, d_pt_free.p, d_Gi.p, d_h.p, d_Cu.p, d_gu.p, d_scale_pt.p, d_cpoints.p,
+                                d_delta_pts.p, d_step_partial.p, d_ccamrec.p, d_cintr.p, cost_rows);
   });
   SweepArgs a = sweep_args(d_ccamrec.p, d_cintr.p, d_cpoints.p);
   if (cost_separate) timed("cost_only", [&] { launch_cost_only(st, a); });
@@ -351,13 +369,15 @@ void mavba_session::candidate_enqueue(double r, ReduceTasks* tail, int* tail_cou
   if (sharded()) allreduce(d_scal.p + SC_CAND_BEGIN, SC_CAND_COUNT, 0);  // only what the candidate wrote: an evaluation enqueued before it keeps its (already global) sums
 }
 
-bool mavba_session::merge_small() const {
-  return merge_on && !sharded() && NI <= 64 && NC <= 8 && NP <= 8192 && dense_spd_solve_is_small(n_mat, chol_struct);
+bool mavba_session::small_window() const {
+  return !sharded() && NI <= 64 && NC <= 8 && NP <= 8192 && dense_spd_solve_is_small(n_mat, chol_struct);
 }
+bool mavba_session::merge_small() const { return merge_on && small_window(); }
 
 void mavba_session::start() {
   { const char* e = std::getenv("MAVBA_MERGE"); merge_on = !e || std::atoi(e) != 0; }  // (read per solve: the tests compare both ways)
   { const char* e = std::getenv("MAVBA_SPECULATE"); speculate_on = !e || std::atoi(e) != 0; }  // (per solve, like MAVBA_MERGE)
+  read_backsub_switch();  // (per solve, like MAVBA_MERGE)
   { const char* e = std::getenv("MAVBA_SWEEP_RIDE_MAX_OBS"); sweep_ride_max_obs = e ? std::max(0ll, std::atoll(e)) : -1; }  // (per solve, like MAVBA_MERGE; unset: no bound)
   decide_persistent();
   evaluate();
