@@ -906,6 +906,8 @@ def rccl_unique_id():
 
 
 def dense_spd_solve(Amat, b, device=-1):
+    """Solves Amat x = b with the reduced camera system's factorisation. Amat is symmetric positive definite; its LOWER
+    triangle is the one that is read. Raises MavbaError if it is not numerically SPD (a NaN in that triangle included)."""
     Amat, b = A.as_f64(Amat), A.as_f64(b)
     x = np.zeros_like(b)
     _check(load().mavba_dense_spd_solve(len(b), _d(Amat), _d(b), _d(x), device))

@@ -901,7 +901,9 @@ int mavba_dense_spd_solve(int32_t n, const double* A, const double* b, double* x
     for (int i = 0; i < n_pad; ++i) at(i, i) = 1.0;
     for (int i = 0; i < n; ++i)
       for (int j = 0; j < n; ++j)
-        if ((i >> 6) >= (j >> 6)) at(i, j) = A[(size_t)i * n + j];
+        // (the caller's LOWER triangle, mirrored inside the diagonal tiles: the factorisation reads a diagonal 16 x 16 block
+        // right of its diagonal, and an entry of the lower triangle - a NaN, say - must not go unread because of that)
+        if ((i >> 6) >= (j >> 6)) at(i, j) = j > i ? A[(size_t)j * n + i] : A[(size_t)i * n + j];
     for (int j = 0; j < n; ++j) at(n_pad, j) = b[j];
     DevBuf<double> dM, dL, dy, dws, dfail;
     dM.upload(M, st); dL.alloc(M.size()); dy.alloc(n_pad); dws.alloc((size_t)2 * n_pad * 64); dfail.alloc(1); dfail.zero(st);

@@ -188,7 +188,8 @@ __global__ void __launch_bounds__(256) k_pose_refine_batch(const PoseItemDev* __
     bool successful = false;
     double rel = 0.0;
     if (!valid) {
-      if (++invalid_steps >= opt.max_num_consecutive_invalid_steps) { termination = MAVBA_TERM_NUMERICAL_FAILURE; ++n_fail; break; }
+      // (ceres returns before this iteration is recorded: it is not among the unsuccessful steps)
+      if (++invalid_steps >= opt.max_num_consecutive_invalid_steps) { termination = MAVBA_TERM_NUMERICAL_FAILURE; break; }
     } else {
       invalid_steps = 0;
       const double new_cost = pose_cost(cand, it.model, kin, u, X, n, loss_b, loss_inv_b, scratch, tid);

@@ -504,7 +504,8 @@ int mavba_session::iterate(int max_iters, int* done) {
     pending_eval = false;
     if (dec.code == LM_INVALID) {
       forget_speculation();
-      if (++invalid_steps >= opt.max_num_consecutive_invalid_steps) { termination = MAVBA_TERM_NUMERICAL_FAILURE; ++n_fail; break; }
+      // (ceres returns before this iteration is recorded: it is not among the unsuccessful steps, and the radius stays)
+      if (++invalid_steps >= opt.max_num_consecutive_invalid_steps) { termination = MAVBA_TERM_NUMERICAL_FAILURE; break; }
     } else {
       invalid_steps = 0;
       if (dec.code == LM_TERM_PTOL) { forget_speculation(); termination = MAVBA_TERM_PARAMETER_TOLERANCE; break; }

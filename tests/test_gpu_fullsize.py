@@ -276,6 +276,16 @@ for n in (130, 700, 1700):
     x0 = np.linalg.solve(A, b)
     worst = max(worst, float(np.abs(x - x0).max() / np.abs(x0).max()))
 print("WORST", worst)
+# pivots that only the elimination makes negative and NaNs in the lower triangle (tests/test_gpu_failure_paths.py): every
+# one reported under this schedule too, and a good solve after each
+from tests.test_gpu_failure_paths import failures_reported
+reported = tried = 0
+after = 0.0
+for n in (200, 777):
+    A, b = _spd(n, n)
+    r, t, w = failures_reported(mavmap_amd, n, A, b)
+    reported += r; tried += t; after = max(after, w)
+print("REPORTED", reported, "OF", tried, "AFTER", after)
 """
 
 
@@ -287,8 +297,11 @@ def test_dense_spd_solve_with_the_other_panel_schedule(mavba, fuse):
     out = subprocess.run([sys.executable, "-c", _FUSE_SNIPPET.format(root=ROOT)], env=env, capture_output=True, text=True,
                          timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
-    worst = float(out.stdout.split("WORST")[1])
+    worst = float(out.stdout.split("WORST")[1].split()[0])
     assert worst < 1e-10, worst
+    words = out.stdout.split("REPORTED")[1].split()   # "REPORTED r OF t AFTER w"
+    assert int(words[0]) == int(words[2]) > 40, out.stdout[-500:]
+    assert float(words[4]) < 1e-10, words[4]
 
 
 _ABORT_SNIPPET = r"""

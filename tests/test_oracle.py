@@ -313,6 +313,36 @@ def test_dense_cholesky_of_oracle(oracle):
     assert rc != 0
 
 
+@pytest.mark.parametrize("solver", ["dense", "sparse"])
+@pytest.mark.parametrize("extra,termination,unsuccessful,radius", [
+    (dict(), A.TERM_NUMERICAL_FAILURE, 9, 2.0 ** -45),
+    (dict(max_num_consecutive_invalid_steps=3), A.TERM_NUMERICAL_FAILURE, 2, 0.125),
+    (dict(min_trust_region_radius=1e-3), A.TERM_PARAMETER_TOLERANCE, 4, 2.0 ** -10)], ids=["limit_10", "limit_3", "min_radius"])
+def test_invalid_steps_are_counted_like_ceres(oracle, solver, extra, termination, unsuccessful, radius):
+    """An LM diagonal clamped to -4 at a radius <= 1 (Jacobi-scaled diagonal entries are s / (1 + sqrt(s))^2 < 1, so every
+    damped entry is <= 1 - 4 / r <= -3): sqrt(diag / radius) is NaN, the Cholesky refuses, every step is invalid. The
+    iteration that exhausts max_num_consecutive_invalid_steps returns before it is recorded (Ceres 1.8
+    trust_region_minimizer.cc): limit - 1 unsuccessful steps, the radius divided limit - 1 times (2, 4, 8, ...), the
+    parameters untouched. A minimum radius reached first ends in PARAMETER_TOLERANCE with every invalid step counted."""
+    p = synth.make_scene(num_images=6, num_points=120, track_len=3, models=[A.MODEL_PINHOLE, A.MODEL_OPENCV], seed=31)
+    bad = global_opts(initial_trust_region_radius=1.0, min_lm_diagonal=-4.0, max_lm_diagonal=-4.0, **extra)
+    for constant_points in (False, True):
+        q = p.copy()
+        if constant_points:
+            q.point_const[:] = 1
+        q0 = q.copy()
+        with oracle.linear_solver(oracle.SPARSE if solver == "sparse" else oracle.DENSE):
+            res, perr = oracle.solve(q, oracle.options(**bad), want_point_errors=True)
+            at_input, perr0 = oracle.solve(q0.copy(), oracle.options(**global_opts(max_num_iterations=0)), want_point_errors=True)
+        assert res["termination"] == termination
+        assert res["num_successful_steps"] == 0 and res["num_unsuccessful_steps"] == unsuccessful
+        assert res["final_trust_region_radius"] == radius
+        assert res["final_cost"] == res["initial_cost"] == at_input["initial_cost"]
+        for name in ("poses", "intrinsics", "points"):
+            assert np.array_equal(getattr(q, name), getattr(q0, name)), name
+        assert np.array_equal(perr, perr0, equal_nan=True)   # the errors at the input parameters
+
+
 def test_regression_fixture(oracle):
     """Frozen oracle output (tests/golden/oracle_solve_regression.json, written by
     tests/golden/make_regression_fixture.py): guards the checker itself against silent edits."""
