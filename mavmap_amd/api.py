@@ -374,6 +374,30 @@ def triangulate_pairs(items, tri_max_reproj_error=4.0, tri_min_angle=2.0, reject
                                 float(arr[q].kernel_seconds)) for q, o in enumerate(outs)]
 
 
+def _ransac_item(c, it, n, sample_size, defaults, trial_outputs, trial_arrays):
+    """What every batched RANSAC call does per item: fills the common fields of the ctypes item `c` (threshold, trial budget,
+    stop, probability, supplied samples or seed) from the item's overrides or `defaults`, and allocates inlier_mask [n] and
+    - with trial_outputs - the per-trial arrays, trial_arrays = {field: (shape behind the trial axis, dtype)}; without, they
+    are empty and their pointers stay NULL. Returns (the samples, to be kept alive, {field: array})."""
+    mt = int(it.get("max_trials", defaults["max_trials"]))
+    smp = it.get("samples")
+    if smp is not None:
+        smp = np.ascontiguousarray(smp, dtype=np.int32).reshape(max(mt, 0), sample_size)
+    c.max_reproj_error_px = float(it.get("max_reproj_error", defaults["max_reproj_error"]))
+    c.max_trials = mt
+    c.stop_num_inliers = int(it.get("stop_num_inliers", defaults["stop_num_inliers"]))
+    c.probability = float(it.get("probability", defaults["probability"]))
+    c.samples = A.ptr(smp, C.c_int32); c.seed = int(it.get("seed", defaults["seed"])) & 0xFFFFFFFFFFFFFFFF
+    k = max(mt, 0) if trial_outputs else 0
+    o = dict(inlier_mask=np.zeros(n, np.uint8))
+    c.inlier_mask = A.ptr(o["inlier_mask"], C.c_uint8)
+    for name, (shape, dtype) in trial_arrays.items():
+        o[name] = np.zeros((k,) + shape, dtype)
+        if trial_outputs:
+            setattr(c, name, A.ptr(o[name], C.c_int32) if dtype is np.int32 else _d(o[name]))
+    return smp, o
+
+
 @dataclass
 class AbsolutePoseResult:
     """What mavba_absolute_pose_ransac returns for one image."""
@@ -411,31 +435,18 @@ def absolute_pose_ransac(items, max_reproj_error=4.0, max_trials=500, stop_num_i
         return []
     arr = (A.CAbsPoseItem * count)()
     hold, outs = [], []
+    defaults = dict(max_reproj_error=max_reproj_error, max_trials=max_trials, stop_num_inliers=stop_num_inliers, probability=probability, seed=seed)
     for q, it in enumerate(items):
         intr, model = _split_camera_params(it["camera_params"])
         uv, xyz = A.as_f64(it["points2D"], (-1, 2)), A.as_f64(it["points3D"], (-1, 3))
         n = len(uv)
         if len(xyz) != n:
             raise ValueError("points2D and points3D differ in length")
-        mt = int(it.get("max_trials", max_trials))
-        smp = it.get("samples")
-        if smp is not None:
-            smp = np.ascontiguousarray(smp, dtype=np.int32).reshape(max(mt, 0), 4)
-        hold.append((intr, uv, xyz, smp))
         c = arr[q]
         c.intrinsics = _d(intr); c.camera_model = model; c.uv = _d(uv); c.xyz = _d(xyz); c.n = n
-        c.max_reproj_error_px = float(it.get("max_reproj_error", max_reproj_error))
-        c.max_trials = mt
-        c.stop_num_inliers = int(it.get("stop_num_inliers", stop_num_inliers))
-        c.probability = float(it.get("probability", probability))
-        c.samples = A.ptr(smp, C.c_int32); c.seed = int(it.get("seed", seed)) & 0xFFFFFFFFFFFFFFFF
-        k = max(mt, 0) if trial_outputs else 0
-        o = dict(inlier_mask=np.zeros(n, np.uint8), trial_models=np.zeros((k, 3, 4)), trial_num_inliers=np.zeros(k, np.int32),
-                 trial_residual_sum=np.zeros(k), trial_samples=np.zeros((k, 4), np.int32))
-        c.inlier_mask = A.ptr(o["inlier_mask"], C.c_uint8)
-        if trial_outputs:
-            c.trial_models = _d(o["trial_models"]); c.trial_num_inliers = A.ptr(o["trial_num_inliers"], C.c_int32)
-            c.trial_residual_sum = _d(o["trial_residual_sum"]); c.trial_samples = A.ptr(o["trial_samples"], C.c_int32)
+        smp, o = _ransac_item(c, it, n, 4, defaults, trial_outputs, dict(
+            trial_models=((3, 4), float), trial_num_inliers=((), np.int32), trial_residual_sum=((), float), trial_samples=((4,), np.int32)))
+        hold.append((intr, uv, xyz, smp))
         outs.append(o)
     _check(load().mavba_absolute_pose_ransac(count, arr, int(device)))
     return [AbsolutePoseResult(int(arr[q].status), np.array(arr[q].rvec), np.array(arr[q].tvec), np.array(arr[q].proj_matrix).reshape(3, 4),
@@ -503,6 +514,7 @@ def relative_pose_ransac(items, max_reproj_error=4.0, max_trials=1000, stop_num_
         return []
     arr = (A.CRelPoseItem * count)()
     hold, outs = [], []
+    defaults = dict(max_reproj_error=max_reproj_error, max_trials=max_trials, stop_num_inliers=stop_num_inliers, probability=probability, seed=seed)
     for q, it in enumerate(items):
         intr1, model1 = _split_camera_params(it["camera_params1"])
         intr2, model2 = _split_camera_params(it["camera_params2"])
@@ -510,28 +522,13 @@ def relative_pose_ransac(items, max_reproj_error=4.0, max_trials=1000, stop_num_
         n = len(uv1)
         if len(uv2) != n:
             raise ValueError("points2D1 and points2D2 differ in length")
-        mt = int(it.get("max_trials", max_trials))
-        smp = it.get("samples")
-        if smp is not None:
-            smp = np.ascontiguousarray(smp, dtype=np.int32).reshape(max(mt, 0), 5)
-        hold.append((intr1, intr2, uv1, uv2, smp))
         c = arr[q]
         c.intrinsics1 = _d(intr1); c.intrinsics2 = _d(intr2); c.camera_model1 = model1; c.camera_model2 = model2
         c.uv1 = _d(uv1); c.uv2 = _d(uv2); c.n = n
-        c.max_reproj_error_px = float(it.get("max_reproj_error", max_reproj_error))
-        c.max_trials = mt
-        c.stop_num_inliers = int(it.get("stop_num_inliers", stop_num_inliers))
-        c.probability = float(it.get("probability", probability))
-        c.samples = A.ptr(smp, C.c_int32); c.seed = int(it.get("seed", seed)) & 0xFFFFFFFFFFFFFFFF
-        k = max(mt, 0) if trial_outputs else 0
-        o = dict(inlier_mask=np.zeros(n, np.uint8), trial_num_models=np.zeros(k, np.int32), trial_models=np.zeros((k, 10, 3, 3)),
-                 trial_z=np.zeros((k, 10)), trial_num_inliers=np.zeros((k, 10), np.int32), trial_residual_sum=np.zeros((k, 10)),
-                 trial_samples=np.zeros((k, 5), np.int32))
-        c.inlier_mask = A.ptr(o["inlier_mask"], C.c_uint8)
-        if trial_outputs:
-            c.trial_num_models = A.ptr(o["trial_num_models"], C.c_int32); c.trial_models = _d(o["trial_models"]); c.trial_z = _d(o["trial_z"])
-            c.trial_num_inliers = A.ptr(o["trial_num_inliers"], C.c_int32); c.trial_residual_sum = _d(o["trial_residual_sum"])
-            c.trial_samples = A.ptr(o["trial_samples"], C.c_int32)
+        smp, o = _ransac_item(c, it, n, 5, defaults, trial_outputs, dict(
+            trial_num_models=((), np.int32), trial_models=((10, 3, 3), float), trial_z=((10,), float), trial_num_inliers=((10,), np.int32),
+            trial_residual_sum=((10,), float), trial_samples=((5,), np.int32)))
+        hold.append((intr1, intr2, uv1, uv2, smp))
         outs.append(o)
     _check(load().mavba_relative_pose_ransac(count, arr, int(device)))
     return [RelativePoseResult(int(arr[q].status), np.array(arr[q].E).reshape(3, 3), np.array(arr[q].R).reshape(3, 3), np.array(arr[q].tvec),

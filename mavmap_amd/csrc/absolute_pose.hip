@@ -17,7 +17,7 @@
 // The item's LAST work-group to finish (an integer ticket, as in triangulate.hip) replays the selection over the trials
 // in trial order, writes the best model's inlier mask and converts R to rvec. No floating-point atomics, no
 // spinning: a work-group never waits for another one.
-#include "session.h"
+#include "batch_call.h"
 #include "dev_reduce.h"
 #include "p3p_math.h"
 
@@ -28,31 +28,15 @@ static_assert(kAbsposeOk == MAVBA_ABSPOSE_OK && kAbsposeNoConsensus == MAVBA_ABS
 constexpr int kAbsTrialsPerWave = 4;
 constexpr int kAbsTrialsPerGroup = 4 * kAbsTrialsPerWave;  // tests/test_gpu_absolute_pose.py runs 15, 16 and 17 trials
 
-struct AbsItemDev {
-  long long pt_begin;       // first point of the item in the packed arrays
-  long long trial_begin;    // first trial of the item in the per-trial arrays
-  long long table_begin;    // first entry (k = 0) of the item's dynamic-limit table
-  long long samples_begin;  // first row of the item's supplied samples, or -1: draw them
-  long long stop;           // stop_num_inliers, <= 0: none
-  unsigned long long seed;
-  double thr;               // the threshold in normalised coordinates
-  int n, max_trials, first_block, num_blocks;
-};
-
 struct AbsResultDev {
   double rvec[3], tvec[3], P[12];
   int num_inliers, best_trial, trials_used, status;
 };
 
-// v of lane `src` (uniform) in every lane, held in scalar registers
-__device__ __forceinline__ double wave_bcast(double v, int src) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-}
-
 // Packed inputs: xy [N] lifted observations, xyz [N] (w unused), samples_in: the supplied rows (sorted), table: the
 // dynamic limits. Per trial: models [T][12], cnt [T], sum [T], samp [T]. mask [N]. done: one ticket counter per item,
 // zero on entry.
-__global__ void __launch_bounds__(256) k_absolute_pose(const AbsItemDev* __restrict__ items, const int2* __restrict__ block_map,
+__global__ void __launch_bounds__(256) k_absolute_pose(const RansacItemDev* __restrict__ items, const int2* __restrict__ block_map,
                                                        const double2* __restrict__ xy, const double4* __restrict__ xyz,
                                                        const int4* __restrict__ samples_in, const int* __restrict__ table, double* models,
                                                        int* cnt, double* sum, int4* samp, unsigned char* mask, unsigned* done,
@@ -63,7 +47,7 @@ __global__ void __launch_bounds__(256) k_absolute_pose(const AbsItemDev* __restr
   __shared__ int s_last, s_end, s_best, s_used, s_inl;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int2 bm = block_map[blockIdx.x];
-  const AbsItemDev& it = items[bm.x];
+  const RansacItemDev& it = items[bm.x];
   const int n = it.n, max_trials = it.max_trials;
   const size_t pb = (size_t)it.pt_begin, tb = (size_t)it.trial_begin;
   const double thr = it.thr;
@@ -149,12 +133,7 @@ __global__ void __launch_bounds__(256) k_absolute_pose(const AbsItemDev* __restr
   }
 
   // ---- the item's last work-group to get here finishes the item ----
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(&done[bm.x], 1u) == (unsigned)(it.num_blocks - 1);
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
+  if (!last_block_of_item(done, bm.x, it.num_blocks, &s_last)) return;
 
   P3PSelect sel;  // (thread 0's)
   for (int base = 0; base < max_trials; base += 256) {
@@ -208,69 +187,41 @@ __global__ void __launch_bounds__(256) k_absolute_pose(const AbsItemDev* __restr
   }
 }
 
-// Host side: validate, lift, pack, one upload per array, one launch, one download per array kind some item asked for.
+// Host side, on the frame of batch_call.h: validate, lift and pack, launch, download, scatter.
 void absolute_pose_ransac(int count, mavba_abspose_item* items, int device) {
-  std::vector<AbsItemDev> hd((size_t)count);
-  long long total = 0, trials = 0, blocks = 0, table_len = 0, rows = 0;
+  // ---- validate: every item is judged before the device is touched ----
+  std::vector<RansacItemDev> hd((size_t)count);
+  RansacBatch batch;
   bool want_mask = false, want_models = false, want_cnt = false, want_sum = false, want_samp = false;
   for (int q = 0; q < count; ++q) {
     const mavba_abspose_item& it = items[q];
-    if (it.n < 0 || it.n > 0x7fffffffLL || it.max_trials < 0 || (it.n > 0 && (!it.intrinsics || !it.uv || !it.xyz)))
-      throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "null or negative argument in absolute-pose item");
-    if (it.camera_model < 1 || it.camera_model > 3) throw Failure(MAVBA_ERR_BAD_MODEL, "bad camera model");
-    AbsItemDev& d = hd[q];
-    std::memset(&d, 0, sizeof(d));
-    d.samples_begin = -1;
-    const bool runs = it.n > 4 && it.max_trials > 0;  // (the others own no work-group and are answered by the host)
-    if (!runs) continue;
-    d.pt_begin = total; d.trial_begin = trials; d.table_begin = table_len; d.stop = it.stop_num_inliers; d.seed = it.seed;
-    d.n = (int)it.n; d.max_trials = it.max_trials; d.first_block = (int)blocks;
-    d.num_blocks = (it.max_trials + kAbsTrialsPerGroup - 1) / kAbsTrialsPerGroup;
-    if (it.samples) {
-      for (long long r = 0; r < 4LL * it.max_trials; r += 4) {
-        const int32_t* s = it.samples + r;
-        bool bad = false;
-        for (int a = 0; a < 4; ++a) {
-          bad |= s[a] < 0 || s[a] >= it.n;
-          for (int b = 0; b < a; ++b) bad |= s[a] == s[b];
-        }
-        if (bad) throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "sample row with a repeated or out-of-range index");
-      }
-      d.samples_begin = rows;
-      rows += it.max_trials;
-    }
-    total += it.n; trials += it.max_trials; blocks += d.num_blocks; table_len += it.n + 1;
+    check_item(it.n, it.max_trials >= 0 && !(it.n > 0 && (!it.intrinsics || !it.uv || !it.xyz)), "absolute-pose");
+    check_model(it.camera_model);
+    if (!(it.n > 4 && it.max_trials > 0)) continue;  // (such an item owns no work-group and is answered by the host)
+    batch.place<4>(hd[q], it.n, it.max_trials, it.stop_num_inliers, it.seed, it.samples, kAbsTrialsPerGroup, 12);
     want_mask |= it.inlier_mask != nullptr; want_models |= it.trial_models != nullptr; want_cnt |= it.trial_num_inliers != nullptr;
     want_sum |= it.trial_residual_sum != nullptr; want_samp |= it.trial_samples != nullptr;
-    if (total > 0x7fffffffLL || trials > 0x7fffffffLL / 12 || blocks > 0x7fffffffLL || table_len > 0x7fffffffLL)
-      throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 points, model entries or work-groups in one batch");
   }
-  if (mavba_device_count() <= 0) throw Failure(MAVBA_ERR_NO_DEVICE, "no HIP device: the mavba backend has no CPU path");
-  // the caller's current device is restored on return
-  struct Restore { int prev = -1; ~Restore() { if (prev >= 0) (void)hipSetDevice(prev); } } restore;
-  if (device >= 0) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = -1; }
-    if (cur != device) { HIP_OK(hipSetDevice(device)); restore.prev = cur; }
-  }
+  require_device();
+  DeviceScope on_device(device);
   double kernel_seconds = 0.0;
   std::vector<AbsResultDev> h_res((size_t)count);
   std::vector<double> h_models, h_sum;
   std::vector<int> h_cnt;
   std::vector<int4> h_samp;
   std::vector<unsigned char> h_mask;
-  if (blocks > 0) {
-    const size_t N = (size_t)total, T = (size_t)trials;
-    std::vector<int2> map((size_t)blocks);
+  if (batch.blocks > 0) {
+    // ---- lift and pack ----
+    const size_t N = (size_t)batch.points, T = (size_t)batch.trials;
+    const std::vector<int2> map = make_block_map(hd, batch.blocks);
     std::vector<double2> xy(N);
     std::vector<double4> xyz(N);
-    std::vector<int4> srows((size_t)rows);
-    std::vector<int> table((size_t)table_len);
+    std::vector<int4> srows((size_t)batch.rows);
+    std::vector<int> table((size_t)batch.table_len);
     for (int q = 0; q < count; ++q) {
       const mavba_abspose_item& it = items[q];
-      AbsItemDev& d = hd[q];
+      RansacItemDev& d = hd[q];
       if (d.num_blocks == 0) continue;
-      for (int c = 0; c < d.num_blocks; ++c) map[(size_t)d.first_block + c] = make_int2(q, c);
       double cam[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
       for (int k = 0; k < model_k(it.camera_model); ++k) cam[k] = it.intrinsics[k];
       d.thr = image2world_threshold(it.max_reproj_error_px, cam);
@@ -289,44 +240,33 @@ void absolute_pose_ransac(int count, mavba_abspose_item* items, int device) {
           srows[(size_t)d.samples_begin + t] = make_int4(a0, a1, a2, a3);
         }
     }
-    hipStream_t st = nullptr;
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    HIP_OK(stream_acquire(&st));
-    struct Release { hipStream_t st; int dev; ~Release() { (void)hipStreamSynchronize(st); release_staged(st); stream_release(st, dev); } } rel{st, dev};
-    struct Events {
-      hipEvent_t a = nullptr, b = nullptr;
-      ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    HIP_OK(hipEventCreate(&ev.a));
-    HIP_OK(hipEventCreate(&ev.b));
-    DevBuf<AbsItemDev> d_items; DevBuf<int2> d_map; DevBuf<double2> d_xy; DevBuf<double4> d_xyz; DevBuf<int4> d_srows, d_samp; DevBuf<int> d_table, d_cnt;
+    // ---- launch ----
+    StreamScope call;
+    hipStream_t st = call.st;
+    DevBuf<RansacItemDev> d_items; DevBuf<int2> d_map; DevBuf<double2> d_xy; DevBuf<double4> d_xyz; DevBuf<int4> d_srows, d_samp; DevBuf<int> d_table, d_cnt;
     DevBuf<double> d_models, d_sum; DevBuf<unsigned char> d_mask; DevBuf<unsigned> d_done; DevBuf<AbsResultDev> d_res;
     d_items.upload(hd, st); d_map.upload(map, st); d_xy.upload(xy, st); d_xyz.upload(xyz, st); d_srows.upload(srows, st); d_table.upload(table, st);
     d_models.alloc(12 * T); d_cnt.alloc(T); d_sum.alloc(T); d_samp.alloc(T); d_mask.alloc(N); d_done.alloc((size_t)count); d_res.alloc((size_t)count);
     d_done.zero(st);
-    HIP_OK(hipEventRecord(ev.a, st));
-    hipLaunchKernelGGL(k_absolute_pose, dim3((unsigned)blocks), dim3(256), 0, st, d_items.p, d_map.p, d_xy.p, d_xyz.p, d_srows.p, d_table.p,
+    call.begin();
+    hipLaunchKernelGGL(k_absolute_pose, dim3((unsigned)batch.blocks), dim3(256), 0, st, d_items.p, d_map.p, d_xy.p, d_xyz.p, d_srows.p, d_table.p,
                        d_models.p, d_cnt.p, d_sum.p, d_samp.p, d_mask.p, d_done.p, d_res.p);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(ev.b, st));
-    HIP_OK(copy_d2h_staged_sync(h_res.data(), d_res.p, h_res.size() * sizeof(AbsResultDev), st));
-    if (want_models) { h_models.resize(12 * T); HIP_OK(copy_d2h_staged_sync(h_models.data(), d_models.p, 12 * T * sizeof(double), st)); }
-    if (want_cnt) { h_cnt.resize(T); HIP_OK(copy_d2h_staged_sync(h_cnt.data(), d_cnt.p, T * sizeof(int), st)); }
-    if (want_sum) { h_sum.resize(T); HIP_OK(copy_d2h_staged_sync(h_sum.data(), d_sum.p, T * sizeof(double), st)); }
-    if (want_samp) { h_samp.resize(T); HIP_OK(copy_d2h_staged_sync(h_samp.data(), d_samp.p, T * sizeof(int4), st)); }
-    if (want_mask) { h_mask.resize(N); HIP_OK(copy_d2h_staged_sync(h_mask.data(), d_mask.p, N, st)); }
-    release_staged(st);
-    HIP_OK(hipGetLastError());
-    float ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&ms, ev.a, ev.b));
-    kernel_seconds = 1e-3 * (double)ms;
+    call.end();
+    // ---- download: one array per kind some item asked for ----
+    call.download(h_res, d_res.p, (size_t)count);
+    call.download(h_models, d_models.p, 12 * T, want_models);
+    call.download(h_cnt, d_cnt.p, T, want_cnt);
+    call.download(h_sum, d_sum.p, T, want_sum);
+    call.download(h_samp, d_samp.p, T, want_samp);
+    call.download(h_mask, d_mask.p, N, want_mask);
+    call.finish();
+    kernel_seconds = call.seconds();
   }
-  // nothing of the caller's was written before this point: an error leaves every output untouched
+  // ---- scatter: nothing of the caller's was written before this point ----
   const double nan = std::numeric_limits<double>::quiet_NaN();
   for (int q = 0; q < count; ++q) {
     mavba_abspose_item& it = items[q];
-    const AbsItemDev& d = hd[q];
+    const RansacItemDev& d = hd[q];
     const size_t n = (size_t)it.n, mt = (size_t)it.max_trials;
     if (d.num_blocks == 0) {  // n <= 4 (the reference's first domain_error) or no trial at all
       AbsResultDev& r = h_res[q];
@@ -355,3 +295,4 @@ void absolute_pose_ransac(int count, mavba_abspose_item* items, int device) {
 }
 
 }  // namespace mavba
+

@@ -1,5 +1,5 @@
 // api.hip - the C ABI of include/mavba.h over the session object (no exception crosses it).
-#include "session.h"
+#include "batch_call.h"
 #include "lm_decide.h"
 
 namespace mavba { thread_local std::string g_last_error; }
@@ -12,23 +12,12 @@ using namespace mavba;
 // ===========================================================================
 #define MAVBA_TRY try {
 // Entry points that work on a session run on the SESSION's device whatever the calling thread's current device is
-// (two sessions on two GPUs driven from one process, or from different threads), and leave the caller's device as it was.
-namespace {
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-    if (prev != dev) HIP_OK(hipSetDevice(dev)); else prev = -1;
-  }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-}  // namespace
+// (two sessions on two GPUs driven from one process, or from different threads), and leave the caller's device as it was
+// (DeviceScope, batch_call.h).
 #define MAVBA_SESSION_TRY(s)                                                    \
   try {                                                                         \
     if (!(s)) throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "null session");        \
-    DeviceGuard device_guard_((s)->device);
+    DeviceScope device_guard_((s)->device);
 #define MAVBA_CATCH                                                              \
   }                                                                              \
   catch (const Failure& f) { g_last_error = f.what(); return f.code; }           \
@@ -79,7 +68,7 @@ int mavba_session_create(const mavba_problem* problem, const mavba_options* opti
   s->opt = *options;
   int dev = options->device;
   if (dev < 0) HIP_OK(hipGetDevice(&dev));  // the calling thread's current device
-  DeviceGuard device_guard_(dev);            // (the caller's current device is restored on return)
+  DeviceScope device_guard_(dev);            // (the caller's current device is restored on return)
   s->device = dev;
   HIP_OK(stream_acquire(&s->st));
   s->build(problem);
@@ -93,9 +82,7 @@ int mavba_session_create(const mavba_problem* problem, const mavba_options* opti
 
 void mavba_session_destroy(mavba_session* s) {
   if (!s) return;
-  int prev = -1;
-  if (hipGetDevice(&prev) == hipSuccess && prev != s->device) (void)hipSetDevice(s->device); else prev = -1;
-  struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore{prev};
+  DeviceScope on_device(s->device, std::nothrow);
   if (!std::getenv("MAVBA_SETUP_TIMING")) { delete s; return; }
   // phase timing of the tear-down (profiling aid)
   double t0 = now_s();
@@ -530,7 +517,7 @@ int mavba_debug_lm_decide(int32_t n, const double* cases, double* out_host, doub
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); throw Failure(MAVBA_ERR_NO_DEVICE, "no HIP device: the mavba backend has no CPU path"); }
   if (n == 0) return MAVBA_OK;
-  DeviceGuard g(device >= 0 ? device : 0);
+  DeviceScope g(device >= 0 ? device : 0);
   double *din = nullptr, *dout = nullptr;
   HIP_OK(hipMalloc(reinterpret_cast<void**>(&din), (size_t)n * (SC_COUNT + 8) * 8));
   HIP_OK(hipMalloc(reinterpret_cast<void**>(&dout), (size_t)n * 6 * 8));
@@ -584,11 +571,9 @@ int64_t mavba_debug_upload_batch(int32_t n, const int64_t* sizes, int64_t arena_
   int64_t wrong = -1;
   try {
     if (device >= 0) HIP_OK(hipSetDevice(device));
-    hipStream_t st;
-    HIP_OK(stream_acquire(&st));
-    int st_dev = 0;
-    (void)hipGetDevice(&st_dev);
-    struct Release { hipStream_t st; int dev; ~Release() { (void)hipStreamSynchronize(st); release_staged(st); stream_release(st, dev); upload_batch_debug_arena(0); } } rel{st, st_dev};
+    struct Arena { ~Arena() { upload_batch_debug_arena(0); } } arena;  // (declared first: back to the default size behind the stream's release)
+    StreamScope call;
+    hipStream_t st = call.st;
     upload_batch_debug_arena((size_t)arena_bytes);
     std::vector<std::unique_ptr<DevBuf<unsigned char>>> bufs;
     std::vector<std::vector<unsigned char>> want;
@@ -704,7 +689,7 @@ int mavba_solve(const mavba_problem* problem, const mavba_options* options, mavb
     // problem.Evaluate runs on the user's blocks (bundle_adjustment.cc:583-588): after NUMERICAL_FAILURE those still hold
     // the parameters the call started from
     if (term == MAVBA_TERM_NUMERICAL_FAILURE) {
-      try { DeviceGuard g(s->device); s->restore_initial_params(); } catch (const std::exception& e) { g_last_error = e.what(); rc = MAVBA_ERR_HIP; }
+      try { DeviceScope g(s->device); s->restore_initial_params(); } catch (const std::exception& e) { g_last_error = e.what(); rc = MAVBA_ERR_HIP; }
     }
     if (rc == MAVBA_OK) rc = mavba_session_point_errors(s, point_error);
   }
@@ -781,7 +766,7 @@ int mavba_solve_filter_solve(const mavba_problem* problem, const mavba_options* 
     rc = mavba_session_get_params(s, problem->poses, problem->intrinsics, problem->points);
   if (rc == MAVBA_OK && point_error) {
     if (term == MAVBA_TERM_NUMERICAL_FAILURE) {
-      try { DeviceGuard g(s->device); s->restore_initial_params(); } catch (const std::exception& e) { g_last_error = e.what(); rc = MAVBA_ERR_HIP; }
+      try { DeviceScope g(s->device); s->restore_initial_params(); } catch (const std::exception& e) { g_last_error = e.what(); rc = MAVBA_ERR_HIP; }
     }
     if (rc == MAVBA_OK) rc = mavba_session_point_errors(s, point_error);
   }
@@ -884,11 +869,8 @@ int mavba_dense_spd_solve(int32_t n, const double* A, const double* b, double* x
   if (mavba_device_count() <= 0) { g_last_error = "no HIP device: the mavba backend has no CPU path"; return MAVBA_ERR_NO_DEVICE; }
   MAVBA_TRY
   if (device >= 0) HIP_OK(hipSetDevice(device));
-  hipStream_t st;
-  HIP_OK(stream_acquire(&st));  // (the cached stream the sessions use: a process that solves one thing at a time stays on one stream)
-  int st_dev = 0;
-  (void)hipGetDevice(&st_dev);
-  struct Release { hipStream_t st; int dev; ~Release() { (void)hipStreamSynchronize(st); release_staged(st); stream_release(st, dev); } } rel{st, st_dev};
+  StreamScope call;  // (the cached stream the sessions use: a process that solves one thing at a time stays on one stream)
+  hipStream_t st = call.st;
   const int n_pad = std::max(64, round_up(n, 64));
   int rc = MAVBA_OK;
   {

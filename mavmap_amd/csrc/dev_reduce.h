@@ -23,6 +23,10 @@ __device__ __forceinline__ double wave_sum(double v) {
   const double r3 = __hiloint2double(__builtin_amdgcn_readlane(hi, 48), __builtin_amdgcn_readlane(lo, 48));
   return (r0 + r1) + (r2 + r3);
 }
+// v of lane `src` (uniform) in every lane, held in scalar registers
+__device__ __forceinline__ double wave_bcast(double v, int src) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
+}
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
@@ -76,6 +80,20 @@ __device__ __forceinline__ double block_max_256(double v, double* scratch) {
   if (lane == 0) scratch[wv] = v;
   __syncthreads();
   return fmax(fmax(scratch[0], scratch[1]), fmax(scratch[2], scratch[3]));
+}
+
+// The ticket of an item that several work-groups of 256 work on: every one takes a ticket when its global stores are
+// done, and the one that takes the last (num_blocks - 1) finishes the item. Returns, to every thread of the group,
+// whether this group is that last one; then the stores of the item's other groups are visible to it (read them with
+// agent-scope atomic loads). done[item] is zero on entry; s_last: one int of LDS. No group waits for another one.
+__device__ __forceinline__ bool last_block_of_item(unsigned* done, int item, int num_blocks, int* s_last) {
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) *s_last = atomicAdd(&done[item], 1u) == (unsigned)(num_blocks - 1);
+  __syncthreads();
+  if (!*s_last) return false;
+  __threadfence();
+  return true;
 }
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

@@ -1,18 +1,18 @@
 // e5_math.h — relative pose from 2D-2D matches: the five-point hypothesis (up to ten essential matrices per sample),
-// the Sampson score, the selection among the (trial, model) sequence of a RANSAC run and the recovery of (R, t).
+// the Sampson score and the recovery of (R, t).
 //
 // These inline functions are the bodies of the kernel in relative_pose.hip. Like p3p_math.h they are
 // __host__ __device__, so tests/ can compile this header with g++ and check it without a GPU.
 // There is no CPU path in the library: nothing here iterates over a batch.
 //
 // What is evaluated (reference file:line):
-//   samples       src/util/estimation.cc:71-93: five distinct indices in ascending order (std::set); the generator is
-//                 p3p_mix of p3p_math.h with rows of five
+//   samples       src/util/estimation.cc:71-93: five distinct indices in ascending order (std::set); the generator,
+//                 the dynamic trial limit and the selection among the (trial, model) sequence are ransac_core.h's.
+//                 A trial without a model never steps the selection: it updates nothing and cannot end the run
 //   hypothesis    EssentialMatrixEstimator::estimate, src/base3d/essential_matrix.cc:12-128, with poly_solve
 //                 (Durand-Kerner), src/util/math.cc:52-87
 //   score         EssentialMatrixEstimator::residuals, src/base3d/essential_matrix.cc:131-162, and
 //                 src/util/estimation.cc:104-117
-//   selection     src/util/estimation.cc:15-21, :98-133
 //   pose          decompose_essential_matrix and pose_from_essential_matrix, src/base3d/essential_matrix.cc:165-269
 //
 // The reference includes two generated files for the 10 x 20 constraint matrix and for the determinant polynomial.
@@ -51,27 +51,15 @@ constexpr int kE5Work = 479;    // (odd: the workspaces of neighbouring lanes st
 // Samples
 // ---------------------------------------------------------------------------
 MAVBA_HD void e5_sort5(int& a0, int& a1, int& a2, int& a3, int& a4) {
-  p3p_cswap(a0, a1); p3p_cswap(a3, a4); p3p_cswap(a2, a4); p3p_cswap(a2, a3); p3p_cswap(a1, a4);
-  p3p_cswap(a0, a3); p3p_cswap(a0, a2); p3p_cswap(a1, a3); p3p_cswap(a1, a2);
+  cswap(a0, a1); cswap(a3, a4); cswap(a2, a4); cswap(a2, a3); cswap(a1, a4);
+  cswap(a0, a3); cswap(a0, a2); cswap(a1, a3); cswap(a1, a2);
 }
 
-MAVBA_HD void e5_row_add(int v, int& a0, int& a1, int& a2, int& a3, int& a4, int& cnt) {
-  const bool add = !(v == a0 || v == a1 || v == a2 || v == a3 || v == a4);
-  a0 = add && cnt == 0 ? v : a0;
-  a1 = add && cnt == 1 ? v : a1;
-  a2 = add && cnt == 2 ? v : a2;
-  a3 = add && cnt == 3 ? v : a3;
-  a4 = add && cnt == 4 ? v : a4;
-  cnt += add ? 1 : 0;
-}
-
-// The row of trial `trial` for n >= 5 points (the call needs n >= 6), ascending: p3p_draw_sample with five entries.
+// The row of trial `trial` for n >= 5 points (the call needs n >= 6), ascending.
 MAVBA_HD void e5_draw_sample(unsigned long long seed, unsigned trial, unsigned n, int& a0, int& a1, int& a2, int& a3, int& a4) {
-  a0 = a1 = a2 = a3 = a4 = -1;
-  int cnt = 0;
-  for (unsigned d = 0; d < (unsigned)kP3PMaxDraws && cnt < 5; ++d)
-    e5_row_add((int)(((p3p_mix(seed, trial, d) >> 32) * (unsigned long long)n) >> 32), a0, a1, a2, a3, a4, cnt);
-  for (int v = 0; cnt < 5; ++v) e5_row_add(v, a0, a1, a2, a3, a4, cnt);
+  int a[5];
+  ransac_draw_row<5>(seed, trial, n, a);
+  a0 = a[0]; a1 = a[1]; a2 = a[2]; a3 = a[3]; a4 = a[4];
   e5_sort5(a0, a1, a2, a3, a4);
 }
 
@@ -402,39 +390,10 @@ MAVBA_HD double e5_residual(const double* E, double x1, double y1, double x2, do
   return num / sqrt(a0 * a0 + a1 * a1 + b0 * b0 + b1 * b1);
 }
 
-// ---------------------------------------------------------------------------
-// Selection
-// ---------------------------------------------------------------------------
-struct E5Select {
-  long long best_inliers = 0;
-  double best_sum = DBL_MAX;
-  int best_trial = -1, best_model = -1;
-  int trials_used = 0;
-};
-
-// estimation.cc:119-133 for model m of trial t. `limit` = the dynamic-limit table at THIS model's count. Returns true
-// when the run ends with this model (the later models of the trial are then ignored). A trial without a model never
-// gets here: it updates nothing and cannot end the run.
-MAVBA_HD bool e5_select_step(E5Select& s, int t, int m, int num_inliers, double residual_sum, int limit, long long stop_num_inliers) {
-  if (num_inliers > s.best_inliers || (num_inliers == s.best_inliers && residual_sum < s.best_sum)) {
-    s.best_inliers = num_inliers;
-    s.best_sum = residual_sum;
-    s.best_trial = t;
-    s.best_model = m;
-  }
-  s.trials_used = t + 1;
-  return (stop_num_inliers > 0 && s.best_inliers >= stop_num_inliers) || t >= limit;
-}
-
-// dynamic_max_trials_(k, n, 5, probability) as a table entry: p3p_dynamic_limit with exponent 5 (HOST libm).
-inline int e5_dynamic_limit(long long k, long long n, double probability) {
-  const double e = 1 - k / (double)n;
-  const double nom = fmax(DBL_MIN, 1 - probability);
-  const double denom = fmax(DBL_MIN, 1 - pow(1 - e, 5.0));
-  const double quot = ceil(log(nom) / log(denom));
-  if (!(quot - quot == 0.0)) return kP3PNoLimit;
-  return quot <= 0.0 ? 0 : (quot >= (double)kP3PNoLimit ? kP3PNoLimit : (int)quot);
-}
+// Selection and trial limit: ransac_core.h's over the (trial, model) sequence - every model that gets here is valid - and samples of five.
+using E5Select = RansacSelect;
+MAVBA_HD bool e5_select_step(E5Select& s, int t, int m, int count, double sum, int limit, long long stop) { return ransac_select_step(s, t, m, true, count, sum, limit, stop); }
+inline int e5_dynamic_limit(long long k, long long n, double probability) { return ransac_dynamic_limit(k, n, 5, probability); }
 
 // ---------------------------------------------------------------------------
 // Pose recovery

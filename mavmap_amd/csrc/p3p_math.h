@@ -1,5 +1,4 @@
-// p3p_math.h — absolute pose from 2D-3D matches: the sample generator, the P3P hypothesis, the score of a model and
-// the selection among the trials of a RANSAC run.
+// p3p_math.h — absolute pose from 2D-3D matches: the sample rows, the P3P hypothesis and the score of a model.
 //
 // These inline functions are the bodies of the kernel in absolute_pose.hip. Like tri_math.h they are
 // __host__ __device__, so tests/ can compile this header with g++ and check it without a GPU.
@@ -7,11 +6,10 @@
 //
 // What is evaluated (reference file:line):
 //   samples       src/util/estimation.cc:71-93: four distinct indices, used in ascending order (std::set); the
-//                 generator itself is this library's (include/mavba_absolute_pose.h writes its recipe out)
+//                 generator, the dynamic trial limit and the selection among the trials are ransac_core.h's
 //   hypothesis    P3PEstimator::estimate, src/base3d/p3p.cc:26-169, with poly_solve (Durand-Kerner),
 //                 src/util/math.cc:52-87, and Eigen::umeyama(src, dst, false)
 //   score         P3PEstimator::residuals, src/base3d/p3p.cc:172-199, and src/util/estimation.cc:104-117
-//   selection     src/util/estimation.cc:15-21, :119-133
 //   rvec          Eigen::AngleAxisd(R), angle times axis, src/sfm/sequential_mapper.cc:710-712
 //
 // Everything up to the model is evaluated operation for operation as written, without fused multiply-adds
@@ -24,50 +22,25 @@
 #include <float.h>
 #include <stdint.h>
 
+#include "ransac_core.h"
 #include "tri_math.h"
 
 namespace mavba {
 
 constexpr int kAbsposeOk = 0, kAbsposeNoConsensus = 1;  // MAVBA_ABSPOSE_* (absolute_pose.hip asserts that they are equal)
-constexpr int kP3PNoLimit = 0x7fffffff;                 // entry of the dynamic-limit table: no limit
-constexpr int kP3PMaxDraws = 64;                        // draws of the generator before a row is completed in order
 
 // ---------------------------------------------------------------------------
-// Samples
+// Samples (the generator is ransac_core.h's; the row is used in ascending order)
 // ---------------------------------------------------------------------------
-MAVBA_HD unsigned long long p3p_mix(unsigned long long seed, unsigned trial, unsigned draw) {
-  unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (((unsigned long long)trial << 32) + (unsigned long long)draw + 1ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-MAVBA_HD void p3p_cswap(int& a, int& b) {
-  const int lo = a < b ? a : b, hi = a < b ? b : a;
-  a = lo; b = hi;
-}
-
 MAVBA_HD void p3p_sort4(int& a0, int& a1, int& a2, int& a3) {
-  p3p_cswap(a0, a1); p3p_cswap(a2, a3); p3p_cswap(a0, a2); p3p_cswap(a1, a3); p3p_cswap(a1, a2);
-}
-
-// appends v to the row (a0..a3, cnt entries) unless the row holds it (selects, not branches: the row stays in registers)
-MAVBA_HD void p3p_row_add(int v, int& a0, int& a1, int& a2, int& a3, int& cnt) {
-  const bool add = !(v == a0 || v == a1 || v == a2 || v == a3);
-  a0 = add && cnt == 0 ? v : a0;
-  a1 = add && cnt == 1 ? v : a1;
-  a2 = add && cnt == 2 ? v : a2;
-  a3 = add && cnt == 3 ? v : a3;
-  cnt += add ? 1 : 0;
+  cswap(a0, a1); cswap(a2, a3); cswap(a0, a2); cswap(a1, a3); cswap(a1, a2);
 }
 
 // The row of trial `trial` for n >= 4 points (the call needs n >= 5), ascending.
 MAVBA_HD void p3p_draw_sample(unsigned long long seed, unsigned trial, unsigned n, int& a0, int& a1, int& a2, int& a3) {
-  a0 = a1 = a2 = a3 = -1;
-  int cnt = 0;
-  for (unsigned d = 0; d < (unsigned)kP3PMaxDraws && cnt < 4; ++d)
-    p3p_row_add((int)(((p3p_mix(seed, trial, d) >> 32) * (unsigned long long)n) >> 32), a0, a1, a2, a3, cnt);
-  for (int v = 0; cnt < 4; ++v) p3p_row_add(v, a0, a1, a2, a3, cnt);
+  int a[4];
+  ransac_draw_row<4>(seed, trial, n, a);
+  a0 = a[0]; a1 = a[1]; a2 = a[2]; a3 = a[3];
   p3p_sort4(a0, a1, a2, a3);
 }
 
@@ -362,38 +335,10 @@ MAVBA_HD bool p3p_estimate(const double* x2d, const double* X, double* M) {
   return false;
 }
 
-// ---------------------------------------------------------------------------
-// Selection
-// ---------------------------------------------------------------------------
-struct P3PSelect {
-  long long best_inliers = 0;
-  double best_sum = DBL_MAX;
-  int best_trial = -1;
-  int trials_used = 0;
-};
-
-// estimation.cc:119-133 for trial t. `limit` = the dynamic-limit table at this trial's count. Returns true when the
-// run ends with this trial. An invalid trial never becomes the best and counts as a trial with no inliers.
-MAVBA_HD bool p3p_select_step(P3PSelect& s, int t, bool valid, int num_inliers, double residual_sum, int limit, long long stop_num_inliers) {
-  if (valid && (num_inliers > s.best_inliers || (num_inliers == s.best_inliers && residual_sum < s.best_sum))) {
-    s.best_inliers = num_inliers;
-    s.best_sum = residual_sum;
-    s.best_trial = t;
-  }
-  s.trials_used = t + 1;
-  return (stop_num_inliers > 0 && s.best_inliers >= stop_num_inliers) || t >= limit;
-}
-
-// dynamic_max_trials_(k, n, 4, probability) as a table entry, with the HOST's log / pow / ceil (a device pow that
-// differs by one ulp would flip a ceil): a quotient that is not finite means no limit, a finite one is clamped.
-inline int p3p_dynamic_limit(long long k, long long n, double probability) {
-  const double e = 1 - k / (double)n;
-  const double nom = fmax(DBL_MIN, 1 - probability);
-  const double denom = fmax(DBL_MIN, 1 - pow(1 - e, 4.0));
-  const double quot = ceil(log(nom) / log(denom));
-  if (!(quot - quot == 0.0)) return kP3PNoLimit;
-  return quot <= 0.0 ? 0 : (quot >= (double)kP3PNoLimit ? kP3PNoLimit : (int)quot);
-}
+// Selection and trial limit: ransac_core.h's with one model per trial, the trial's own `valid` flag and samples of four.
+using P3PSelect = RansacSelect;
+MAVBA_HD bool p3p_select_step(P3PSelect& s, int t, bool valid, int count, double sum, int limit, long long stop) { return ransac_select_step(s, t, 0, valid, count, sum, limit, stop); }
+inline int p3p_dynamic_limit(long long k, long long n, double probability) { return ransac_dynamic_limit(k, n, 4, probability); }
 
 // ---------------------------------------------------------------------------
 // rvec

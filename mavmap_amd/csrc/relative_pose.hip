@@ -19,7 +19,7 @@
 // (trial, model) sequence, writes the best model's inlier mask, counts the four pose candidates' points in front of
 // both cameras and converts the chosen R to rvec. No floating-point atomics, no spinning: a work-group never waits
 // for another one.
-#include "session.h"
+#include "batch_call.h"
 #include "dev_reduce.h"
 #include "e5_math.h"
 
@@ -32,31 +32,15 @@ constexpr int kRelTrialsPerGroup = 4 * kRelTrialsPerWave;  // tests/test_gpu_rel
 constexpr int kRelReplayChunk = 256;                        // trials per pass of the selection replay
 static_assert(kRelReplayChunk * (kE5MaxModels * 3 + 1) / 2 + 8 <= kRelTrialsPerGroup * kE5Work, "the replay's tables fit in the workspaces");
 
-struct RelItemDev {
-  long long pt_begin;       // first point of the item in the packed arrays
-  long long trial_begin;    // first trial of the item in the per-trial arrays
-  long long table_begin;    // first entry (k = 0) of the item's dynamic-limit table
-  long long samples_begin;  // first row of the item's supplied samples, or -1: draw them
-  long long stop;           // stop_num_inliers, <= 0: none
-  unsigned long long seed;
-  double thr;               // the threshold in normalised coordinates
-  int n, max_trials, first_block, num_blocks;
-};
-
 struct RelResultDev {
   double E[9], R[9], tvec[3], rvec[3], forward_z;
   int cheir[4], cheir_best, num_inliers, best_trial, best_model, trials_used, status;
 };
 
-// v of lane `src` (uniform) in every lane, held in scalar registers
-__device__ __forceinline__ double rel_bcast(double v, int src) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-}
-
 // Packed inputs: pts [N] = (x1, y1, x2, y2) lifted, samples_in: the supplied rows [.][5] (sorted), table: the dynamic
 // limits. Per trial: nmod [T], samp [T][5]; per (trial, model): models [T][10][9], zs [T][10], cnt [T][10], sum [T][10].
 // mask [N]. done: one ticket counter per item, zero on entry.
-__global__ void __launch_bounds__(256) k_relative_pose(const RelItemDev* __restrict__ items, const int2* __restrict__ block_map,
+__global__ void __launch_bounds__(256) k_relative_pose(const RansacItemDev* __restrict__ items, const int2* __restrict__ block_map,
                                                        const double4* __restrict__ pts, const int* __restrict__ samples_in,
                                                        const int* __restrict__ table, int* nmod, double* models, double* zs, int* cnt,
                                                        double* sum, int* samp, unsigned char* mask, unsigned* done, RelResultDev* results) {
@@ -66,7 +50,7 @@ __global__ void __launch_bounds__(256) k_relative_pose(const RelItemDev* __restr
   __shared__ int s_last, s_end, s_best, s_bestm, s_used, s_inl, s_ch[4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int2 bm = block_map[blockIdx.x];
-  const RelItemDev& it = items[bm.x];
+  const RansacItemDev& it = items[bm.x];
   const int n = it.n, max_trials = it.max_trials;
   const size_t pb = (size_t)it.pt_begin, tb = (size_t)it.trial_begin;
   const double thr = it.thr;
@@ -114,7 +98,7 @@ __global__ void __launch_bounds__(256) k_relative_pose(const RelItemDev* __restr
       if (m < nm) {
         double E[9];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) E[k] = rel_bcast(ws[kE5Models + 9 * m + k], 0);
+        for (int k = 0; k < 9; ++k) E[k] = wave_bcast(ws[kE5Models + 9 * m + k], 0);
         for (int i = lane; i < n; i += 64) {
           const double4 p = pts[pb + i];
           const double r = fabs(e5_residual(E, p.x, p.y, p.z, p.w));
@@ -130,12 +114,7 @@ __global__ void __launch_bounds__(256) k_relative_pose(const RelItemDev* __restr
   }
 
   // ---- the item's last work-group to get here finishes the item ----
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(&done[bm.x], 1u) == (unsigned)(it.num_blocks - 1);
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
+  if (!last_block_of_item(done, bm.x, it.num_blocks, &s_last)) return;
 
   // the replay's tables lie over the workspaces, which are no longer needed
   double* r_sum = s_ws;                                                            // [256][10]
@@ -230,68 +209,41 @@ __global__ void __launch_bounds__(256) k_relative_pose(const RelItemDev* __restr
   }
 }
 
-// Host side: validate, lift, pack, one upload per array, one launch, one download per array kind some item asked for.
+// Host side, on the frame of batch_call.h: validate, lift and pack, launch, download, scatter.
 void relative_pose_ransac(int count, mavba_relpose_item* items, int device) {
-  std::vector<RelItemDev> hd((size_t)count);
-  long long total = 0, trials = 0, blocks = 0, table_len = 0, rows = 0;
+  // ---- validate: every item is judged before the device is touched ----
+  std::vector<RansacItemDev> hd((size_t)count);
+  RansacBatch batch;
   bool want_mask = false, want_nm = false, want_models = false, want_z = false, want_cnt = false, want_sum = false, want_samp = false;
   for (int q = 0; q < count; ++q) {
     const mavba_relpose_item& it = items[q];
-    if (it.n < 0 || it.n > 0x7fffffffLL || it.max_trials < 0 || (it.n > 0 && (!it.intrinsics1 || !it.intrinsics2 || !it.uv1 || !it.uv2)))
-      throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "null or negative argument in relative-pose item");
-    if (it.camera_model1 < 1 || it.camera_model1 > 3 || it.camera_model2 < 1 || it.camera_model2 > 3) throw Failure(MAVBA_ERR_BAD_MODEL, "bad camera model");
-    RelItemDev& d = hd[q];
-    std::memset(&d, 0, sizeof(d));
-    d.samples_begin = -1;
-    const bool runs = it.n > 5 && it.max_trials > 0;  // (the others own no work-group and are answered by the host)
-    if (!runs) continue;
-    d.pt_begin = total; d.trial_begin = trials; d.table_begin = table_len; d.stop = it.stop_num_inliers; d.seed = it.seed;
-    d.n = (int)it.n; d.max_trials = it.max_trials; d.first_block = (int)blocks;
-    d.num_blocks = (it.max_trials + kRelTrialsPerGroup - 1) / kRelTrialsPerGroup;
-    if (it.samples) {
-      for (long long r = 0; r < 5LL * it.max_trials; r += 5) {
-        const int32_t* s = it.samples + r;
-        bool bad = false;
-        for (int a = 0; a < 5; ++a) {
-          bad |= s[a] < 0 || s[a] >= it.n;
-          for (int b = 0; b < a; ++b) bad |= s[a] == s[b];
-        }
-        if (bad) throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "sample row with a repeated or out-of-range index");
-      }
-      d.samples_begin = rows;
-      rows += it.max_trials;
-    }
-    total += it.n; trials += it.max_trials; blocks += d.num_blocks; table_len += it.n + 1;
+    check_item(it.n, it.max_trials >= 0 && !(it.n > 0 && (!it.intrinsics1 || !it.intrinsics2 || !it.uv1 || !it.uv2)), "relative-pose");
+    check_model(it.camera_model1);
+    check_model(it.camera_model2);
+    if (!(it.n > 5 && it.max_trials > 0)) continue;  // (such an item owns no work-group and is answered by the host)
+    batch.place<5>(hd[q], it.n, it.max_trials, it.stop_num_inliers, it.seed, it.samples, kRelTrialsPerGroup, 9 * kE5MaxModels);
     want_mask |= it.inlier_mask != nullptr; want_nm |= it.trial_num_models != nullptr; want_models |= it.trial_models != nullptr;
     want_z |= it.trial_z != nullptr; want_cnt |= it.trial_num_inliers != nullptr; want_sum |= it.trial_residual_sum != nullptr;
     want_samp |= it.trial_samples != nullptr;
-    if (total > 0x7fffffffLL || trials > 0x7fffffffLL / 90 || blocks > 0x7fffffffLL || table_len > 0x7fffffffLL)
-      throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 points, model entries or work-groups in one batch");
   }
-  if (mavba_device_count() <= 0) throw Failure(MAVBA_ERR_NO_DEVICE, "no HIP device: the mavba backend has no CPU path");
-  // the caller's current device is restored on return
-  struct Restore { int prev = -1; ~Restore() { if (prev >= 0) (void)hipSetDevice(prev); } } restore;
-  if (device >= 0) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = -1; }
-    if (cur != device) { HIP_OK(hipSetDevice(device)); restore.prev = cur; }
-  }
+  require_device();
+  DeviceScope on_device(device);
   double kernel_seconds = 0.0;
   std::vector<RelResultDev> h_res((size_t)count);
   std::vector<double> h_models, h_z, h_sum;
   std::vector<int> h_nm, h_cnt, h_samp;
   std::vector<unsigned char> h_mask;
-  if (blocks > 0) {
-    const size_t N = (size_t)total, T = (size_t)trials;
-    std::vector<int2> map((size_t)blocks);
+  if (batch.blocks > 0) {
+    // ---- lift and pack ----
+    const size_t N = (size_t)batch.points, T = (size_t)batch.trials;
+    const std::vector<int2> map = make_block_map(hd, batch.blocks);
     std::vector<double4> pts(N);
-    std::vector<int> srows(5 * (size_t)rows);
-    std::vector<int> table((size_t)table_len);
+    std::vector<int> srows(5 * (size_t)batch.rows);
+    std::vector<int> table((size_t)batch.table_len);
     for (int q = 0; q < count; ++q) {
       const mavba_relpose_item& it = items[q];
-      RelItemDev& d = hd[q];
+      RansacItemDev& d = hd[q];
       if (d.num_blocks == 0) continue;
-      for (int c = 0; c < d.num_blocks; ++c) map[(size_t)d.first_block + c] = make_int2(q, c);
       double cam1[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, cam2[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
       for (int k = 0; k < model_k(it.camera_model1); ++k) cam1[k] = it.intrinsics1[k];
       for (int k = 0; k < model_k(it.camera_model2); ++k) cam2[k] = it.intrinsics2[k];
@@ -312,47 +264,36 @@ void relative_pose_ransac(int count, mavba_relpose_item* items, int device) {
           o[0] = a0; o[1] = a1; o[2] = a2; o[3] = a3; o[4] = a4;
         }
     }
-    hipStream_t st = nullptr;
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    HIP_OK(stream_acquire(&st));
-    struct Release { hipStream_t st; int dev; ~Release() { (void)hipStreamSynchronize(st); release_staged(st); stream_release(st, dev); } } rel{st, dev};
-    struct Events {
-      hipEvent_t a = nullptr, b = nullptr;
-      ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    HIP_OK(hipEventCreate(&ev.a));
-    HIP_OK(hipEventCreate(&ev.b));
-    DevBuf<RelItemDev> d_items; DevBuf<int2> d_map; DevBuf<double4> d_pts; DevBuf<int> d_srows, d_table, d_nm, d_cnt, d_samp;
+    // ---- launch ----
+    StreamScope call;
+    hipStream_t st = call.st;
+    DevBuf<RansacItemDev> d_items; DevBuf<int2> d_map; DevBuf<double4> d_pts; DevBuf<int> d_srows, d_table, d_nm, d_cnt, d_samp;
     DevBuf<double> d_models, d_z, d_sum; DevBuf<unsigned char> d_mask; DevBuf<unsigned> d_done; DevBuf<RelResultDev> d_res;
     d_items.upload(hd, st); d_map.upload(map, st); d_pts.upload(pts, st); d_srows.upload(srows, st); d_table.upload(table, st);
     d_nm.alloc(T); d_models.alloc(90 * T); d_z.alloc(10 * T); d_cnt.alloc(10 * T); d_sum.alloc(10 * T); d_samp.alloc(5 * T); d_mask.alloc(N);
     d_done.alloc((size_t)count); d_res.alloc((size_t)count);
     d_done.zero(st);
-    HIP_OK(hipEventRecord(ev.a, st));
-    hipLaunchKernelGGL(k_relative_pose, dim3((unsigned)blocks), dim3(256), 0, st, d_items.p, d_map.p, d_pts.p, d_srows.p, d_table.p, d_nm.p,
+    call.begin();
+    hipLaunchKernelGGL(k_relative_pose, dim3((unsigned)batch.blocks), dim3(256), 0, st, d_items.p, d_map.p, d_pts.p, d_srows.p, d_table.p, d_nm.p,
                        d_models.p, d_z.p, d_cnt.p, d_sum.p, d_samp.p, d_mask.p, d_done.p, d_res.p);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(ev.b, st));
-    HIP_OK(copy_d2h_staged_sync(h_res.data(), d_res.p, h_res.size() * sizeof(RelResultDev), st));
-    if (want_nm) { h_nm.resize(T); HIP_OK(copy_d2h_staged_sync(h_nm.data(), d_nm.p, T * sizeof(int), st)); }
-    if (want_models) { h_models.resize(90 * T); HIP_OK(copy_d2h_staged_sync(h_models.data(), d_models.p, 90 * T * sizeof(double), st)); }
-    if (want_z) { h_z.resize(10 * T); HIP_OK(copy_d2h_staged_sync(h_z.data(), d_z.p, 10 * T * sizeof(double), st)); }
-    if (want_cnt) { h_cnt.resize(10 * T); HIP_OK(copy_d2h_staged_sync(h_cnt.data(), d_cnt.p, 10 * T * sizeof(int), st)); }
-    if (want_sum) { h_sum.resize(10 * T); HIP_OK(copy_d2h_staged_sync(h_sum.data(), d_sum.p, 10 * T * sizeof(double), st)); }
-    if (want_samp) { h_samp.resize(5 * T); HIP_OK(copy_d2h_staged_sync(h_samp.data(), d_samp.p, 5 * T * sizeof(int), st)); }
-    if (want_mask) { h_mask.resize(N); HIP_OK(copy_d2h_staged_sync(h_mask.data(), d_mask.p, N, st)); }
-    release_staged(st);
-    HIP_OK(hipGetLastError());
-    float ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&ms, ev.a, ev.b));
-    kernel_seconds = 1e-3 * (double)ms;
+    call.end();
+    // ---- download: one array per kind some item asked for ----
+    call.download(h_res, d_res.p, (size_t)count);
+    call.download(h_nm, d_nm.p, T, want_nm);
+    call.download(h_models, d_models.p, 90 * T, want_models);
+    call.download(h_z, d_z.p, 10 * T, want_z);
+    call.download(h_cnt, d_cnt.p, 10 * T, want_cnt);
+    call.download(h_sum, d_sum.p, 10 * T, want_sum);
+    call.download(h_samp, d_samp.p, 5 * T, want_samp);
+    call.download(h_mask, d_mask.p, N, want_mask);
+    call.finish();
+    kernel_seconds = call.seconds();
   }
-  // nothing of the caller's was written before this point: an error leaves every output untouched
+  // ---- scatter: nothing of the caller's was written before this point ----
   const double nan = std::numeric_limits<double>::quiet_NaN();
   for (int q = 0; q < count; ++q) {
     mavba_relpose_item& it = items[q];
-    const RelItemDev& d = hd[q];
+    const RansacItemDev& d = hd[q];
     const size_t n = (size_t)it.n, mt = (size_t)it.max_trials;
     if (d.num_blocks == 0) {  // n <= 5 (the reference's first domain_error) or no trial at all
       RelResultDev& r = h_res[q];
@@ -389,3 +330,4 @@ void relative_pose_ransac(int count, mavba_relpose_item* items, int device) {
 }
 
 }  // namespace mavba
+

@@ -20,7 +20,7 @@
 //    bundle_adjustment.cc:228-387) runs in kernels, the session is built from the arrays where they are
 //    (device_setup.hip), and the refined points are scattered back into the resident arrays. Same flat problem, element
 //    for element, as the host route (tests compare the two solves bit for bit).
-#include "session.h"
+#include "batch_call.h"
 
 using namespace mavba;
 
@@ -378,12 +378,7 @@ int mavba_scene::device_bundle_adjust(const long long* const lists[3], const int
     throw Failure(MAVBA_ERR_BAD_INDEX, "no rotation constraint for an image that needs one");
   };
   // the scene lives on the device of its first big call; later calls run there whatever the calling thread's device is
-  struct Restore { int d = -1; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore;
-  if (dev.device >= 0) {
-    int cur = -1;
-    HIP_OK(hipGetDevice(&cur));
-    if (cur != dev.device) { HIP_OK(hipSetDevice(dev.device)); restore.d = cur; }
-  }
+  DeviceScope on_device(dev.device);
   sync_device();
   hipStream_t st = dev.st;
   const int n2 = (int)p2d_set.size(), n3 = (int)p3d_alive.size();

@@ -16,7 +16,7 @@
 //   compaction    the same last work-group walks the item's status words chunk by chunk: ballot + popcount of the
 //                 lanes below inside a wave, the four wave counts and the running base across waves and chunks
 // No floating-point atomics, no spinning: a work-group never waits for another one.
-#include "session.h"
+#include "batch_call.h"
 #include "dev_reduce.h"
 #include "tri_math.h"
 
@@ -77,12 +77,7 @@ __global__ void __launch_bounds__(256) k_triangulate_pairs(const TriItemDev* __r
   if (tid == 0) part_angle[blockIdx.x] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
 
   // the item's last work-group to get here finishes the item
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(&done[bm.x], 1u) == (unsigned)(it.num_blocks - 1);
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
+  if (!last_block_of_item(done, bm.x, it.num_blocks, &s_last)) return;
 
   if (tid == 0) {
     double s = 0.0;
@@ -112,16 +107,17 @@ __global__ void __launch_bounds__(256) k_triangulate_pairs(const TriItemDev* __r
   if (tid == 0) num_accepted[bm.x] = base;
 }
 
-// Host side: validate, pack, one upload per array, one launch, one download per array kind some item asked for.
+// Host side, on the frame of batch_call.h: validate, pack, launch, download, scatter.
 void triangulate_pairs(int count, mavba_tri_pair* items, int device) {
+  // ---- validate: every item is judged before the device is touched ----
   std::vector<TriItemDev> hd((size_t)count);
   long long total = 0, blocks = 0;
   bool tracks = false, want_xyz = false, want_angle = false, want_err = false, want_depth = false, want_status = false, want_acc = false;
   for (int q = 0; q < count; ++q) {
     const mavba_tri_pair& it = items[q];
-    if (it.n < 0 || it.n > 0x7fffffffLL || (it.n > 0 && (!it.intrinsics1 || !it.intrinsics2 || !it.uv1 || !it.uv2)) || (it.has_xyz && !it.xyz_in))
-      throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "null or negative argument in triangulation item");
-    if (it.camera_model1 < 1 || it.camera_model1 > 3 || it.camera_model2 < 1 || it.camera_model2 > 3) throw Failure(MAVBA_ERR_BAD_MODEL, "bad camera model");
+    check_item(it.n, !(it.n > 0 && (!it.intrinsics1 || !it.intrinsics2 || !it.uv1 || !it.uv2)) && !(it.has_xyz && !it.xyz_in), "triangulation");
+    check_model(it.camera_model1);
+    check_model(it.camera_model2);
     TriItemDev& d = hd[q];
     std::memset(&d, 0, sizeof(d));
     d.begin = total; d.n = (int)it.n; d.first_block = (int)blocks; d.num_blocks = (int)((it.n + 255) / 256);
@@ -133,54 +129,38 @@ void triangulate_pairs(int count, mavba_tri_pair* items, int device) {
       tri_pair_prepare(it.rvec1, it.tvec1, it.rvec2, it.tvec2, d.rec);
       d.thr_n = image2world_threshold(it.max_reproj_error_px, d.cam2);
       d.min_angle_rad = tri_min_angle_rad(it.min_angle_deg);
-    }
-    total += it.n; blocks += d.num_blocks;
-    if (it.n > 0) {
       tracks |= it.has_xyz != nullptr;
       want_xyz |= it.xyz != nullptr; want_angle |= it.angle != nullptr; want_err |= it.reproj_error != nullptr;
       want_depth |= it.depth != nullptr; want_status |= it.status != nullptr; want_acc |= it.accepted != nullptr;
     }
-    if (total > 0x7fffffffLL) throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 correspondences in one batch");
+    total += it.n; blocks += d.num_blocks;
+    if (total > kBatchMax) throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 correspondences in one batch");
   }
-  if (mavba_device_count() <= 0) throw Failure(MAVBA_ERR_NO_DEVICE, "no HIP device: the mavba backend has no CPU path");
-  // the caller's current device is restored on return
-  struct Restore { int prev = -1; ~Restore() { if (prev >= 0) (void)hipSetDevice(prev); } } restore;
-  if (device >= 0) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = -1; }
-    if (cur != device) { HIP_OK(hipSetDevice(device)); restore.prev = cur; }
-  }
+  require_device();
+  DeviceScope on_device(device);
   double kernel_seconds = 0.0;
   std::vector<int> h_num((size_t)count, 0);
   std::vector<double> h_mean((size_t)count, std::numeric_limits<double>::quiet_NaN());  // n == 0: 0 / 0
   std::vector<double> h_xyz, h_angle, h_err, h_depth;
   std::vector<int> h_status, h_acc;
   if (blocks > 0) {
+    // ---- pack ----
     const size_t N = (size_t)total;
-    std::vector<int2> map((size_t)blocks);
+    const std::vector<int2> map = make_block_map(hd, blocks);
     std::vector<double4> uv(N);
     std::vector<unsigned char> has(tracks ? N : 0, 0);
     std::vector<double> xin(tracks ? 3 * N : 0, 0.0);
     for (int q = 0; q < count; ++q) {
       const mavba_tri_pair& it = items[q];
       const size_t b = (size_t)hd[q].begin;
-      for (int c = 0; c < hd[q].num_blocks; ++c) map[(size_t)hd[q].first_block + c] = make_int2(q, c);
       for (size_t i = 0; i < (size_t)it.n; ++i) uv[b + i] = make_double4(it.uv1[2 * i], it.uv1[2 * i + 1], it.uv2[2 * i], it.uv2[2 * i + 1]);
       if (it.has_xyz)
         for (size_t i = 0; i < (size_t)it.n; ++i)
           if (it.has_xyz[i]) { has[b + i] = 1; xin[3 * (b + i)] = it.xyz_in[3 * i]; xin[3 * (b + i) + 1] = it.xyz_in[3 * i + 1]; xin[3 * (b + i) + 2] = it.xyz_in[3 * i + 2]; }
     }
-    hipStream_t st = nullptr;
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    HIP_OK(stream_acquire(&st));
-    struct Release { hipStream_t st; int dev; ~Release() { (void)hipStreamSynchronize(st); release_staged(st); stream_release(st, dev); } } rel{st, dev};
-    struct Events {
-      hipEvent_t a = nullptr, b = nullptr;
-      ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    HIP_OK(hipEventCreate(&ev.a));
-    HIP_OK(hipEventCreate(&ev.b));
+    // ---- launch ----
+    StreamScope call;
+    hipStream_t st = call.st;
     DevBuf<TriItemDev> d_items; DevBuf<int2> d_map; DevBuf<double4> d_uv; DevBuf<unsigned char> d_has; DevBuf<double> d_xin;
     DevBuf<double> d_xyz, d_angle, d_err, d_part, d_mean; DevBuf<double2> d_depth; DevBuf<int> d_status, d_acc, d_num; DevBuf<unsigned> d_done;
     d_items.upload(hd, st); d_map.upload(map, st); d_uv.upload(uv, st);
@@ -188,31 +168,27 @@ void triangulate_pairs(int count, mavba_tri_pair* items, int device) {
     d_xyz.alloc(3 * N); d_angle.alloc(N); d_err.alloc(N); d_depth.alloc(N); d_status.alloc(N); d_acc.alloc(N);
     d_part.alloc((size_t)blocks); d_mean.alloc((size_t)count); d_num.alloc((size_t)count); d_done.alloc((size_t)count);
     d_done.zero(st);
-    HIP_OK(hipEventRecord(ev.a, st));
+    call.begin();
     hipLaunchKernelGGL(k_triangulate_pairs, dim3((unsigned)blocks), dim3(256), 0, st, d_items.p, d_map.p, d_uv.p, d_has.p, d_xin.p, d_xyz.p,
                        d_angle.p, d_err.p, d_depth.p, d_status.p, d_acc.p, d_part.p, d_done.p, d_num.p, d_mean.p);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipEventRecord(ev.b, st));
-    // items with n == 0 own no work-group: their slots keep the host's values
-    std::vector<int> num((size_t)count);
-    std::vector<double> mean((size_t)count);
-    HIP_OK(copy_d2h_staged_sync(num.data(), d_num.p, num.size() * sizeof(int), st));
-    HIP_OK(copy_d2h_staged_sync(mean.data(), d_mean.p, mean.size() * sizeof(double), st));
-    for (int q = 0; q < count; ++q)
+    call.end();
+    // ---- download: one array per kind some item asked for ----
+    std::vector<int> num;
+    std::vector<double> mean;
+    call.download(num, d_num.p, (size_t)count);
+    call.download(mean, d_mean.p, (size_t)count);
+    for (int q = 0; q < count; ++q)  // (items with n == 0 own no work-group: their slots keep the host's values)
       if (hd[q].n > 0) { h_num[q] = num[q]; h_mean[q] = mean[q]; }
-    if (want_xyz) { h_xyz.resize(3 * N); HIP_OK(copy_d2h_staged_sync(h_xyz.data(), d_xyz.p, 3 * N * sizeof(double), st)); }
-    if (want_angle) { h_angle.resize(N); HIP_OK(copy_d2h_staged_sync(h_angle.data(), d_angle.p, N * sizeof(double), st)); }
-    if (want_err) { h_err.resize(N); HIP_OK(copy_d2h_staged_sync(h_err.data(), d_err.p, N * sizeof(double), st)); }
-    if (want_depth) { h_depth.resize(2 * N); HIP_OK(copy_d2h_staged_sync(h_depth.data(), d_depth.p, 2 * N * sizeof(double), st)); }
-    if (want_status) { h_status.resize(N); HIP_OK(copy_d2h_staged_sync(h_status.data(), d_status.p, N * sizeof(int), st)); }
-    if (want_acc) { h_acc.resize(N); HIP_OK(copy_d2h_staged_sync(h_acc.data(), d_acc.p, N * sizeof(int), st)); }
-    release_staged(st);
-    HIP_OK(hipGetLastError());
-    float ms = 0.0f;
-    HIP_OK(hipEventElapsedTime(&ms, ev.a, ev.b));
-    kernel_seconds = 1e-3 * (double)ms;
+    call.download(h_xyz, d_xyz.p, 3 * N, want_xyz);
+    call.download(h_angle, d_angle.p, N, want_angle);
+    call.download(h_err, d_err.p, N, want_err);
+    call.download(h_depth, d_depth.p, 2 * N, want_depth);
+    call.download(h_status, d_status.p, N, want_status);
+    call.download(h_acc, d_acc.p, N, want_acc);
+    call.finish();
+    kernel_seconds = call.seconds();
   }
-  // nothing of the caller's was written before this point: an error leaves every output untouched
+  // ---- scatter: nothing of the caller's was written before this point ----
   for (int q = 0; q < count; ++q) {
     mavba_tri_pair& it = items[q];
     const size_t b = (size_t)hd[q].begin, n = (size_t)it.n;

@@ -463,7 +463,7 @@ def host():
 def load_host():
     src = os.path.join(HERE, "host", "e5_math_host.cpp")
     so = os.path.join(HERE, "host", "_e5_math_host.so")
-    hdrs = [os.path.join(ROOT, "mavmap_amd", "csrc", h) for h in ("e5_math.h", "p3p_math.h", "tri_math.h", "ba_math.h")]
+    hdrs = [os.path.join(ROOT, "mavmap_amd", "csrc", h) for h in ("e5_math.h", "p3p_math.h", "ransac_core.h", "tri_math.h", "ba_math.h")]
     hdrs.append(os.path.join(ROOT, "include", "mavba_relative_pose.h"))
     if not os.path.exists(so) or max(os.path.getmtime(f) for f in [src] + hdrs) > os.path.getmtime(so):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, src])
