@@ -1,4 +1,4 @@
-"""ctypes mirror of include/mavba.h, include/mavba_triangulate.h, include/mavba_absolute_pose.h and include/mavba_relative_pose.h (structs and constants only — no library here).
+"""ctypes mirror of include/mavba.h, include/mavba_triangulate.h, include/mavba_absolute_pose.h, include/mavba_relative_pose.h and include/mavba_homography.h (structs and constants only — no library here).
 
 Shared by the product wrapper (mavmap_amd.api) and, in tests/, by the oracle
 loader, so both sides of a parity test see byte-identical problem memory.
@@ -126,6 +126,20 @@ class CRelPoseItem(C.Structure):
                 ("cheirality_counts", C.c_int32 * 4), ("cheirality_best", C.c_int32), ("forward_z", C.c_double),
                 ("num_inliers", C.c_int32), ("best_trial", C.c_int32), ("best_model", C.c_int32), ("trials_used", C.c_int32),
                 ("status", C.c_int32), ("kernel_seconds", C.c_double)]
+
+
+# item status of mavba_homography_ransac (an item result, not a call error)
+HOMOGRAPHY_OK, HOMOGRAPHY_NO_CONSENSUS = 0, 1
+
+
+class CHomographyItem(C.Structure):
+    _fields_ = [("uv1", _dp), ("uv2", _dp), ("n", C.c_int64),
+                ("max_reproj_error_px", C.c_double), ("max_trials", C.c_int32), ("stop_num_inliers", C.c_int64),
+                ("probability", C.c_double), ("samples", _ip), ("seed", C.c_uint64),
+                ("inlier_mask", _bp), ("trial_models", _dp), ("trial_num_inliers", _ip), ("trial_residual_sum", _dp),
+                ("trial_samples", _ip),
+                ("H", C.c_double * 9), ("num_inliers", C.c_int32), ("inlier_ratio", C.c_double),
+                ("best_trial", C.c_int32), ("trials_used", C.c_int32), ("status", C.c_int32), ("kernel_seconds", C.c_double)]
 
 
 class CSceneOptions(C.Structure):

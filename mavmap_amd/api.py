@@ -45,6 +45,8 @@ TRIANGULATE_SYMBOLS = ["mavba_triangulate_pairs"]
 ABSPOSE_SYMBOLS = ["mavba_absolute_pose_ransac"]
 # include/mavba_relative_pose.h, likewise
 RELPOSE_SYMBOLS = ["mavba_relative_pose_ransac"]
+# include/mavba_homography.h, likewise
+HOMOGRAPHY_SYMBOLS = ["mavba_homography_ransac"]
 # include/mavba_backsub_tiles.h, likewise
 BACKSUB_TILES_SYMBOLS = ["mavba_debug_backsub_tiles"]
 
@@ -125,6 +127,8 @@ def load():
     L.mavba_absolute_pose_ransac.restype = C.c_int
     L.mavba_relative_pose_ransac.argtypes = [C.c_int32, C.POINTER(A.CRelPoseItem), C.c_int32]
     L.mavba_relative_pose_ransac.restype = C.c_int
+    L.mavba_homography_ransac.argtypes = [C.c_int32, C.POINTER(A.CHomographyItem), C.c_int32]
+    L.mavba_homography_ransac.restype = C.c_int
     L.mavba_session_set_params.argtypes = [sp, dp, dp, dp]
     L.mavba_session_restart.argtypes = [sp]
     L.mavba_session_filter_points.argtypes = [sp, C.c_double, bp, bp, dp, C.POINTER(C.c_int64)]
@@ -556,6 +560,78 @@ def to_triangulate_pairs(items, results, tri_max_reproj_error=4.0, tri_min_angle
                         points2D1=A.as_f64(it["points2D1"], (-1, 2))[inl], points2D2=A.as_f64(it["points2D2"], (-1, 2))[inl],
                         tri_max_reproj_error=tri_max_reproj_error, tri_min_angle=tri_min_angle, reject=A.TRI_REJECT_INITIAL))
     return out
+
+
+@dataclass
+class HomographyResult:
+    """What mavba_homography_ransac returns for one image pair."""
+    status: int                     # HOMOGRAPHY_OK / HOMOGRAPHY_NO_CONSENSUS
+    H: np.ndarray                   # [3, 3] = trial_models[best_trial] (NaN without consensus); H (x, y, 1) ~ (u, v, 1)
+    num_inliers: int
+    inlier_ratio: float             # num_inliers / n (0 for n == 0)
+    best_trial: int
+    trials_used: int
+    inlier_mask: np.ndarray         # [n] uint8
+    trial_models: np.ndarray        # [max_trials, 3, 3]; NaN for an invalid trial
+    trial_num_inliers: np.ndarray   # [max_trials] int32
+    trial_residual_sum: np.ndarray  # [max_trials]
+    trial_samples: np.ndarray       # [max_trials, 4] int32, ascending
+    kernel_seconds: float
+
+    @property
+    def ok(self):
+        return self.status == A.HOMOGRAPHY_OK
+
+
+def homography_ransac(items, max_reproj_error=4.0, max_trials=100, stop_num_inliers=0, probability=0.99, seed=0, device=-1,
+                      trial_outputs=True):
+    """The view-change test of image pairs: a four-point homography inside RANSAC, many pairs in one launch
+    (mavba_homography_ransac; reference src/sfm/sequential_mapper.cc:116-158 and :465-503). The result of an item is that
+    of the reference's RANSAC() run on one thread with the same samples.
+
+    `items`: list of dicts with points2D1 / points2D2 [n, 2] in pixels, as in relative_pose_ransac; they are used as they
+    are (no camera model, camera_params* are ignored) and max_reproj_error is the threshold in pixels. An item may
+    override max_reproj_error, max_trials, stop_num_inliers (absolute, <= 0: none; see view_change_stop), probability and
+    seed, and may supply samples [max_trials, 4]; otherwise the library draws them from `seed`. trial_outputs=False leaves
+    the per-trial arrays out (they come back empty). Returns one HomographyResult per item."""
+    count = len(items)
+    if count == 0:
+        return []
+    arr = (A.CHomographyItem * count)()
+    hold, outs = [], []
+    defaults = dict(max_reproj_error=max_reproj_error, max_trials=max_trials, stop_num_inliers=stop_num_inliers, probability=probability, seed=seed)
+    for q, it in enumerate(items):
+        uv1, uv2 = A.as_f64(it["points2D1"], (-1, 2)), A.as_f64(it["points2D2"], (-1, 2))
+        n = len(uv1)
+        if len(uv2) != n:
+            raise ValueError("points2D1 and points2D2 differ in length")
+        c = arr[q]
+        c.uv1 = _d(uv1); c.uv2 = _d(uv2); c.n = n
+        smp, o = _ransac_item(c, it, n, 4, defaults, trial_outputs, dict(
+            trial_models=((3, 3), float), trial_num_inliers=((), np.int32), trial_residual_sum=((), float), trial_samples=((4,), np.int32)))
+        hold.append((uv1, uv2, smp))
+        outs.append(o)
+    _check(load().mavba_homography_ransac(count, arr, int(device)))
+    return [HomographyResult(int(arr[q].status), np.array(arr[q].H).reshape(3, 3), int(arr[q].num_inliers), float(arr[q].inlier_ratio),
+                             int(arr[q].best_trial), int(arr[q].trials_used), o["inlier_mask"], o["trial_models"],
+                             o["trial_num_inliers"], o["trial_residual_sum"], o["trial_samples"], float(arr[q].kernel_seconds))
+            for q, o in enumerate(outs)]
+
+
+def view_change_stop(n, max_homography_inliers):
+    """stop_num_inliers of the mapper's view-change test for a pair of n matches: int(n * max_homography_inliers), the
+    size_t of sequential_mapper.cc:131-132. A 0 is passed as 1: the library reads 0 as "no stop", where the reference
+    would stop at once, after its first trial - as the library does at 1 as soon as a trial has an inlier."""
+    return max(int(n * max_homography_inliers), 1)
+
+
+def view_change_pairs(items, results, max_homography_inliers=0.7):
+    """The positions in `items` of the pairs the mapper would keep after homography_ransac: a pair is kept when
+    num_inliers / n <= max_homography_inliers, the test of sequential_mapper.cc:153-156 (it discards a pair that one
+    homography explains: too little parallax, a planar scene or a pure rotation). A pair without consensus - fewer than
+    five matches, or no trial with four inliers - is kept as well: no homography explains it. (The reference does not
+    get that far: its RANSAC() throws there.) The positions select the items to hand to relative_pose_ransac."""
+    return [q for q, r in enumerate(results) if r.status != A.HOMOGRAPHY_OK or r.inlier_ratio <= max_homography_inliers]
 
 
 class Scene:

@@ -819,6 +819,17 @@ int mavba_relative_pose_ransac(int32_t count, mavba_relpose_item* items, int32_t
   MAVBA_CATCH
 }
 
+// The view-change test of image pairs, a four-point homography inside RANSAC (homography.hip): replaces the host step of
+// src/sfm/sequential_mapper.cc:116-158 and :465-503 before a pair goes on to relative or absolute pose.
+int mavba_homography_ransac(int32_t count, mavba_homography_item* items, int32_t device) {
+  if (count < 0 || (count > 0 && !items)) { g_last_error = "null argument"; return MAVBA_ERR_INVALID_ARGUMENT; }
+  if (count == 0) return MAVBA_OK;
+  MAVBA_TRY
+  homography_ransac(count, items, device);  // (arguments first, then the device: an invalid call says so on any machine)
+  return MAVBA_OK;
+  MAVBA_CATCH
+}
+
 int mavba_pose_refine(double rvec[3], double tvec[3], const double* intrinsics, int32_t camera_model,
                       const double* uv, const double* xyz, const uint8_t* inlier_mask, int64_t n,
                       const mavba_options* options, mavba_result* result) {

@@ -27,6 +27,7 @@
 #include "../../include/mavba_backsub_tiles.h"
 #include "../../include/mavba_absolute_pose.h"
 #include "../../include/mavba_relative_pose.h"
+#include "../../include/mavba_homography.h"
 #include "ba_math.h"
 #include "internal.h"
 
@@ -107,6 +108,9 @@ void absolute_pose_ransac(int count, mavba_abspose_item* items, int device);
 
 // relative_pose.hip
 void relative_pose_ransac(int count, mavba_relpose_item* items, int device);
+
+// homography.hip
+void homography_ransac(int count, mavba_homography_item* items, int device);
 
 // host_util.hip
 void rccl_unique_id(void* out128);
