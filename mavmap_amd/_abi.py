@@ -1,4 +1,4 @@
-"""ctypes mirror of include/mavba.h, include/mavba_triangulate.h, include/mavba_absolute_pose.h, include/mavba_relative_pose.h and include/mavba_homography.h (structs and constants only — no library here).
+"""ctypes mirror of include/mavba.h, include/mavba_triangulate.h, include/mavba_absolute_pose.h, include/mavba_relative_pose.h, include/mavba_homography.h and include/mavba_match.h (structs and constants only — no library here).
 
 Shared by the product wrapper (mavmap_amd.api) and, in tests/, by the oracle
 loader, so both sides of a parity test see byte-identical problem memory.
@@ -142,6 +142,17 @@ class CHomographyItem(C.Structure):
                 ("best_trial", C.c_int32), ("trials_used", C.c_int32), ("status", C.c_int32), ("kernel_seconds", C.c_double)]
 
 
+_fp = C.POINTER(C.c_float)
+
+
+# include/mavba_match.h
+class CMatchItem(C.Structure):
+    _fields_ = [("desc1", _fp), ("desc2", _fp), ("xy1", _fp), ("xy2", _fp), ("n1", C.c_int64), ("n2", C.c_int64),
+                ("dim", C.c_int32), ("max_ratio", C.c_double), ("max_distance", C.c_double),
+                ("matches", _ip), ("distances", _fp), ("nn12", _ip), ("dist12", _fp), ("nn21", _ip), ("dist21", _fp),
+                ("num_matches", C.c_int32), ("median_disparity", C.c_double), ("kernel_seconds", C.c_double)]
+
+
 class CSceneOptions(C.Structure):
     _fields_ = [("min_track_len", C.c_int32), ("refine_camera_params", C.c_int32), ("constrain_rotation", C.c_int32),
                 ("constrain_rotation_weight", C.c_double)]
@@ -167,6 +178,13 @@ def ptr(a, ctype):
         return C.cast(None, C.POINTER(ctype))
     assert a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(C.POINTER(ctype))
+
+
+def as_f32(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if shape is not None:
+        a = a.reshape(shape)
+    return a
 
 
 def as_f64(a, shape=None):

@@ -47,6 +47,8 @@ ABSPOSE_SYMBOLS = ["mavba_absolute_pose_ransac"]
 RELPOSE_SYMBOLS = ["mavba_relative_pose_ransac"]
 # include/mavba_homography.h, likewise
 HOMOGRAPHY_SYMBOLS = ["mavba_homography_ransac"]
+# include/mavba_match.h, likewise
+MATCH_SYMBOLS = ["mavba_match_descriptors"]
 # include/mavba_backsub_tiles.h, likewise
 BACKSUB_TILES_SYMBOLS = ["mavba_debug_backsub_tiles"]
 
@@ -129,6 +131,8 @@ def load():
     L.mavba_relative_pose_ransac.restype = C.c_int
     L.mavba_homography_ransac.argtypes = [C.c_int32, C.POINTER(A.CHomographyItem), C.c_int32]
     L.mavba_homography_ransac.restype = C.c_int
+    L.mavba_match_descriptors.argtypes = [C.c_int32, C.POINTER(A.CMatchItem), C.c_int32]
+    L.mavba_match_descriptors.restype = C.c_int
     L.mavba_session_set_params.argtypes = [sp, dp, dp, dp]
     L.mavba_session_restart.argtypes = [sp]
     L.mavba_session_filter_points.argtypes = [sp, C.c_double, bp, bp, dp, C.POINTER(C.c_int64)]
@@ -632,6 +636,77 @@ def view_change_pairs(items, results, max_homography_inliers=0.7):
     five matches, or no trial with four inliers - is kept as well: no homography explains it. (The reference does not
     get that far: its RANSAC() throws there.) The positions select the items to hand to relative_pose_ransac."""
     return [q for q, r in enumerate(results) if r.status != A.HOMOGRAPHY_OK or r.inlier_ratio <= max_homography_inliers]
+
+
+@dataclass
+class MatchResult:
+    """What mavba_match_descriptors returns for one image pair."""
+    matches: np.ndarray           # [num_matches, 2] int32: (index in image 1, index in image 2), ascending in the first
+    distances: np.ndarray         # [num_matches] float32: the descriptor distance of every match
+    nn12: np.ndarray              # [n1, 2] int32: the two nearest candidates in image 2 (-1: absent)
+    dist12: np.ndarray            # [n1, 2] float32 (NaN: absent)
+    nn21: np.ndarray              # [n2, 2] int32
+    dist21: np.ndarray            # [n2, 2] float32
+    median_disparity: float       # NaN without matches or without keypoints
+    kernel_seconds: float
+
+    @property
+    def num_matches(self):
+        return len(self.matches)
+
+
+def match_descriptors(items, max_ratio=0.9, max_distance=-1.0, device=-1):
+    """The 2D-2D matches of image pairs by brute force - two nearest neighbours in both directions, Lowe's ratio test
+    on both sides, the mutual-nearest check - many pairs in two launches (mavba_match_descriptors; reference
+    src/base2d/feature.cc:52-102 as src/sfm/sequential_mapper.cc:2079-2083 calls it). include/mavba_match.h states the
+    rules the result follows.
+
+    `items`: list of dicts with descriptors1 [n1, dim] / descriptors2 [n2, dim] (float32; dim a multiple of 4, at most
+    128) and keypoints1 [n1, 2] / keypoints2 [n2, 2] in pixels. The keypoints may be left out when max_distance < 0 (no
+    spatial mask); the median disparity is then NaN. An item may override max_ratio and max_distance. Returns one
+    MatchResult per item."""
+    count = len(items)
+    if count == 0:
+        return []
+    arr = (A.CMatchItem * count)()
+    hold, outs = [], []
+    f, i32 = C.c_float, C.c_int32
+    for q, it in enumerate(items):
+        d1, d2 = A.as_f32(it["descriptors1"]), A.as_f32(it["descriptors2"])
+        if d1.ndim != 2 or d2.ndim != 2 or d1.shape[1] != d2.shape[1]:
+            raise ValueError("descriptors1 and descriptors2 must be [n, dim] with the same dim")
+        n1, n2, dim = len(d1), len(d2), d1.shape[1]
+        xy1 = None if it.get("keypoints1") is None else A.as_f32(it["keypoints1"], (-1, 2))
+        xy2 = None if it.get("keypoints2") is None else A.as_f32(it["keypoints2"], (-1, 2))
+        if (xy1 is not None and len(xy1) != n1) or (xy2 is not None and len(xy2) != n2):
+            raise ValueError("keypoints and descriptors differ in length")
+        m = min(n1, n2)
+        o = dict(matches=np.zeros((m, 2), np.int32), distances=np.zeros(m, np.float32),
+                 nn12=np.zeros((n1, 2), np.int32), dist12=np.zeros((n1, 2), np.float32),
+                 nn21=np.zeros((n2, 2), np.int32), dist21=np.zeros((n2, 2), np.float32))
+        c = arr[q]
+        c.desc1, c.desc2, c.xy1, c.xy2 = A.ptr(d1, f), A.ptr(d2, f), A.ptr(xy1, f), A.ptr(xy2, f)
+        c.n1, c.n2, c.dim = n1, n2, dim
+        c.max_ratio, c.max_distance = float(it.get("max_ratio", max_ratio)), float(it.get("max_distance", max_distance))
+        c.matches, c.distances = A.ptr(o["matches"], i32), A.ptr(o["distances"], f)
+        c.nn12, c.dist12, c.nn21, c.dist21 = A.ptr(o["nn12"], i32), A.ptr(o["dist12"], f), A.ptr(o["nn21"], i32), A.ptr(o["dist21"], f)
+        hold.append((d1, d2, xy1, xy2))
+        outs.append(o)
+    _check(load().mavba_match_descriptors(count, arr, int(device)))
+    return [MatchResult(o["matches"][:arr[q].num_matches], o["distances"][:arr[q].num_matches], o["nn12"], o["dist12"], o["nn21"], o["dist21"],
+                        float(arr[q].median_disparity), float(arr[q].kernel_seconds)) for q, o in enumerate(outs)]
+
+
+def to_homography_items(items, results):
+    """The items of homography_ransac (and, with camera_params*, of relative_pose_ransac) for the pairs of
+    match_descriptors: points2D1 / points2D2 are the keypoints of every match, in the order of the matches. Every other
+    key of an item (camera_params1, ...) is passed on."""
+    out = []
+    for it, r in zip(items, results):
+        xy1, xy2 = A.as_f64(it["keypoints1"], (-1, 2)), A.as_f64(it["keypoints2"], (-1, 2))
+        keep = {k: v for k, v in it.items() if k not in ("descriptors1", "descriptors2", "keypoints1", "keypoints2", "max_ratio", "max_distance")}
+        out.append(dict(keep, points2D1=xy1[r.matches[:, 0]], points2D2=xy2[r.matches[:, 1]]))
+    return out
 
 
 class Scene:

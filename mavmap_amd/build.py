@@ -13,10 +13,10 @@ CSRC = os.path.join(ROOT, "csrc")
 LIBDIR = os.path.join(ROOT, "lib")
 LIB = os.path.join(LIBDIR, "libmavba.so")
 OBJDIR = os.path.join(LIBDIR, "obj")
-SOURCES = ["kernels.hip", "schur_rows.hip", "dense_chol.hip", "pose_refine.hip", "triangulate.hip", "absolute_pose.hip", "relative_pose.hip", "homography.hip", "host_util.hip", "session_build.hip", "session_lm.hip", "scene.hip", "multi_gpu.hip", "device_setup.hip", "api.hip"]
-HEADERS = ["ba_math.h", "tri_math.h", "ransac_core.h", "p3p_math.h", "e5_math.h", "h4_math.h", "batch_call.h", "dev_reduce.h", "internal.h", "session.h", "lm_decide.h", "lm_bodies.h", "sweep_body.h", "launch_dispatch.h", os.path.join("..", "..", "include", "mavba.h"),
+SOURCES = ["kernels.hip", "schur_rows.hip", "dense_chol.hip", "pose_refine.hip", "triangulate.hip", "absolute_pose.hip", "relative_pose.hip", "homography.hip", "match.hip", "host_util.hip", "session_build.hip", "session_lm.hip", "scene.hip", "multi_gpu.hip", "device_setup.hip", "api.hip"]
+HEADERS = ["ba_math.h", "tri_math.h", "ransac_core.h", "p3p_math.h", "e5_math.h", "h4_math.h", "match_math.h", "batch_call.h", "dev_reduce.h", "internal.h", "session.h", "lm_decide.h", "lm_bodies.h", "sweep_body.h", "launch_dispatch.h", os.path.join("..", "..", "include", "mavba.h"),
            os.path.join("..", "..", "include", "mavba_triangulate.h"), os.path.join("..", "..", "include", "mavba_absolute_pose.h"),
-           os.path.join("..", "..", "include", "mavba_relative_pose.h"), os.path.join("..", "..", "include", "mavba_homography.h"),
+           os.path.join("..", "..", "include", "mavba_relative_pose.h"), os.path.join("..", "..", "include", "mavba_homography.h"), os.path.join("..", "..", "include", "mavba_match.h"),
            os.path.join("..", "..", "include", "mavba_backsub_tiles.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wall",
          "-Wno-unused-result"]

@@ -830,6 +830,17 @@ int mavba_homography_ransac(int32_t count, mavba_homography_item* items, int32_t
   MAVBA_CATCH
 }
 
+// The 2D-2D matches of image pairs, brute-force two nearest neighbours with the ratio test and the cross-check
+// (match.hip): replaces match_brute_force() of src/base2d/feature.cc:52-102 as src/sfm/sequential_mapper.cc:2079-2083 calls it.
+int mavba_match_descriptors(int32_t count, mavba_match_item* items, int32_t device) {
+  if (count < 0 || (count > 0 && !items)) { g_last_error = "null argument"; return MAVBA_ERR_INVALID_ARGUMENT; }
+  if (count == 0) return MAVBA_OK;
+  MAVBA_TRY
+  match_descriptors(count, items, device);  // (arguments first, then the device: an invalid call says so on any machine)
+  return MAVBA_OK;
+  MAVBA_CATCH
+}
+
 int mavba_pose_refine(double rvec[3], double tvec[3], const double* intrinsics, int32_t camera_model,
                       const double* uv, const double* xyz, const uint8_t* inlier_mask, int64_t n,
                       const mavba_options* options, mavba_result* result) {

@@ -28,6 +28,7 @@
 #include "../../include/mavba_absolute_pose.h"
 #include "../../include/mavba_relative_pose.h"
 #include "../../include/mavba_homography.h"
+#include "../../include/mavba_match.h"
 #include "ba_math.h"
 #include "internal.h"
 
@@ -111,6 +112,9 @@ void relative_pose_ransac(int count, mavba_relpose_item* items, int device);
 
 // homography.hip
 void homography_ransac(int count, mavba_homography_item* items, int device);
+
+// match.hip
+void match_descriptors(int count, mavba_match_item* items, int device);
 
 // host_util.hip
 void rccl_unique_id(void* out128);
