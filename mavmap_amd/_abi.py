@@ -196,3 +196,7 @@ def as_f64(a, shape=None):
 
 # scalars of an LM iteration on the device (csrc/internal.h, SC_*): the layout mavba_debug_lm_decide takes
 SC_COST, SC_XNORM2, SC_GRAD_MAX, SC_NEW_COST, SC_STEP_NORM2, SC_MODEL_CHANGE, SC_CAND_XNORM2, SC_FAIL, SC_FAIL_FRONT = range(9)
+
+# mavba_debug_obs_math: kinds, and (doubles in, doubles out) per case (csrc/ba_math.h, obs_math_case)
+OBS_MATH_RCP, OBS_MATH_RSQRT, OBS_MATH_LOG, OBS_MATH_ROT_COEFFS, OBS_MATH_CAUCHY, OBS_MATH_JACOBIAN, OBS_MATH_RESIDUAL, OBS_MATH_BACKSUB = range(8)
+OBS_MATH_WIDTHS = ((1, 1), (1, 1), (1, 1), (1, 3), (2, 2), (21, 38), (21, 2), (36, 5))

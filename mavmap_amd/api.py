@@ -51,6 +51,8 @@ HOMOGRAPHY_SYMBOLS = ["mavba_homography_ransac"]
 MATCH_SYMBOLS = ["mavba_match_descriptors"]
 # include/mavba_backsub_tiles.h, likewise
 BACKSUB_TILES_SYMBOLS = ["mavba_debug_backsub_tiles"]
+# include/mavba_obs_math.h, likewise
+OBS_MATH_SYMBOLS = ["mavba_debug_obs_math"]
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
 
@@ -140,6 +142,8 @@ def load():
     L.mavba_debug_elimination_tree.argtypes = [C.c_int32, C.c_int32, C.c_int64, ip, ip, C.c_int32, ip, ip, C.c_int32]
     L.mavba_debug_radix_sort.argtypes = [C.c_int32, C.POINTER(C.c_uint32), C.c_int32, ip, C.c_int32]
     L.mavba_debug_lm_decide.argtypes = [C.c_int32, dp, dp, dp, C.c_int32]
+    L.mavba_debug_obs_math.argtypes = [C.c_int32, C.c_int32, dp, dp, dp, C.c_int32]
+    L.mavba_debug_obs_math.restype = C.c_int
     L.mavba_debug_backsub_tiles.argtypes = [C.c_int32, ip, ip, C.c_int32]
     L.mavba_debug_backsub_tiles.restype = C.c_int
     i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
@@ -1019,6 +1023,17 @@ def debug_lm_decide(cases, device=-1):
     assert cases.shape[1] == 24
     oh, od = np.zeros((n, 6)), np.zeros((n, 6))
     _check(load().mavba_debug_lm_decide(n, _d(cases), _d(oh), _d(od), device))
+    return oh, od
+
+
+def debug_obs_math(kind, cases, device=-1):
+    """One per-observation function of csrc/ba_math.h (kind: _abi.OBS_MATH_*) on the rows of `cases`: (host build's results,
+    device build's results), _abi.OBS_MATH_WIDTHS[kind][1] columns each."""
+    wi, wo = A.OBS_MATH_WIDTHS[kind]
+    cases = np.ascontiguousarray(cases, dtype=np.float64).reshape(-1, wi)
+    n = cases.shape[0]
+    oh, od = np.zeros((n, wo)), np.zeros((n, wo))
+    _check(load().mavba_debug_obs_math(kind, n, _d(cases), _d(oh), _d(od), device))
     return oh, od
 
 

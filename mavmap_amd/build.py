@@ -17,7 +17,7 @@ SOURCES = ["kernels.hip", "schur_rows.hip", "dense_chol.hip", "pose_refine.hip",
 HEADERS = ["ba_math.h", "tri_math.h", "ransac_core.h", "p3p_math.h", "e5_math.h", "h4_math.h", "match_math.h", "batch_call.h", "dev_reduce.h", "internal.h", "session.h", "lm_decide.h", "lm_bodies.h", "sweep_body.h", "launch_dispatch.h", os.path.join("..", "..", "include", "mavba.h"),
            os.path.join("..", "..", "include", "mavba_triangulate.h"), os.path.join("..", "..", "include", "mavba_absolute_pose.h"),
            os.path.join("..", "..", "include", "mavba_relative_pose.h"), os.path.join("..", "..", "include", "mavba_homography.h"), os.path.join("..", "..", "include", "mavba_match.h"),
-           os.path.join("..", "..", "include", "mavba_backsub_tiles.h")]
+           os.path.join("..", "..", "include", "mavba_backsub_tiles.h"), os.path.join("..", "..", "include", "mavba_obs_math.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wall",
          "-Wno-unused-result"]
 # Per-file additions. dense_chol.hip: matrix instructions with their accumulators in ordinary vector registers - the

@@ -1,6 +1,7 @@
 // api.hip - the C ABI of include/mavba.h over the session object (no exception crosses it).
 #include "batch_call.h"
 #include "lm_decide.h"
+#include "../../include/mavba_obs_math.h"
 
 namespace mavba { thread_local std::string g_last_error; }
 
@@ -524,6 +525,30 @@ int mavba_debug_lm_decide(int32_t n, const double* cases, double* out_host, doub
   HIP_OK(hipMemcpy(din, cases, (size_t)n * (SC_COUNT + 8) * 8, hipMemcpyHostToDevice));
   launch_lm_decide_cases(nullptr, n, din, dout);
   HIP_OK(hipMemcpy(out_device, dout, (size_t)n * 6 * 8, hipMemcpyDeviceToHost));
+  (void)hipFree(din); (void)hipFree(dout);
+  return MAVBA_OK;
+  MAVBA_CATCH
+}
+
+// Test entry: the per-observation functions of ba_math.h (obs_math_case: kinds and widths) by the host build and by the
+// device build on the same `n` cases. The host build divides, takes square roots and calls the library's log where the device
+// build runs its own seeds and series, so the two are compared with a high-precision reference and not with each other.
+int mavba_debug_obs_math(int32_t kind, int32_t n, const double* in, double* out_host, double* out_device, int32_t device) {
+  MAVBA_TRY
+  if (kind < 0 || kind >= MAVBA_OBS_MATH_KINDS || n < 0 || (n > 0 && (!in || !out_host || !out_device)))
+    throw Failure(MAVBA_ERR_INVALID_ARGUMENT, "bad argument");
+  const size_t wi = (size_t)obs_math_in_width(kind), wo = (size_t)obs_math_out_width(kind);
+  for (int c = 0; c < n; ++c) obs_math_case(kind, in + (size_t)c * wi, out_host + (size_t)c * wo);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); throw Failure(MAVBA_ERR_NO_DEVICE, "no HIP device: the mavba backend has no CPU path"); }
+  if (n == 0) return MAVBA_OK;
+  DeviceScope g(device >= 0 ? device : 0);
+  double *din = nullptr, *dout = nullptr;
+  HIP_OK(hipMalloc(reinterpret_cast<void**>(&din), (size_t)n * wi * 8));
+  HIP_OK(hipMalloc(reinterpret_cast<void**>(&dout), (size_t)n * wo * 8));
+  HIP_OK(hipMemcpy(din, in, (size_t)n * wi * 8, hipMemcpyHostToDevice));
+  launch_obs_math_cases(nullptr, kind, n, din, dout);
+  HIP_OK(hipMemcpy(out_device, dout, (size_t)n * wo * 8, hipMemcpyDeviceToHost));
   (void)hipFree(din); (void)hipFree(dout);
   return MAVBA_OK;
   MAVBA_CATCH

@@ -42,17 +42,30 @@ namespace mavba {
 //   Jl(w) = I + b [w]x + c [w]x^2          c = (th - sin th)/th^3
 // 9 doubles = 72 B per image, so 2000 images fit the 160 KB LDS of one CU.
 // ---------------------------------------------------------------------------
+// The closed forms cancel for small th: 1 - cos th keeps an absolute error of 1e-16 of a value th^2 / 2 and th - sin th one of
+// 1e-16 th of a value th^3 / 6, so with the switch at th2 = 1e-6 (as it stood until tests/test_gpu_obs_math.py measured it
+// against a 60-digit reference) b lost 6 digits and c lost 7 just above the switch, and c was still short of 1e-14 at
+// th = 0.3. The series therefore runs to th = 0.5, eight terms each (the first one dropped is below 1e-19 of the sum); above
+// it the closed forms are good to a few ulp.
 MAVBA_HD void rot_coeffs(double th2, double& a, double& b, double& c) {
-  if (th2 > 1e-6) {
+  if (th2 > 0.25) {
     const double th = sqrt(th2);
     const double s = sin(th), co = cos(th);
     a = s / th;
     b = (1.0 - co) / th2;
     c = (th - s) / (th2 * th);
-  } else {  // series; truncation error < th^6/5040 < 2e-22
-    a = 1.0 - th2 * (1.0 / 6.0 - th2 / 120.0);
-    b = 0.5 - th2 * (1.0 / 24.0 - th2 / 720.0);
-    c = 1.0 / 6.0 - th2 * (1.0 / 120.0 - th2 / 5040.0);
+  } else {  // sum_k (-th2)^k / (2k + 1)!, / (2k + 2)!, / (2k + 3)!
+    const double x = -th2;
+    double pa = 1.0 / 1307674368000.0, pb = 1.0 / 20922789888000.0, pc = 1.0 / 355687428096000.0;
+    pa = __builtin_fma(pa, x, 1.0 / 6227020800.0); pb = __builtin_fma(pb, x, 1.0 / 87178291200.0); pc = __builtin_fma(pc, x, 1.0 / 1307674368000.0);
+    pa = __builtin_fma(pa, x, 1.0 / 39916800.0);   pb = __builtin_fma(pb, x, 1.0 / 479001600.0);   pc = __builtin_fma(pc, x, 1.0 / 6227020800.0);
+    pa = __builtin_fma(pa, x, 1.0 / 362880.0);     pb = __builtin_fma(pb, x, 1.0 / 3628800.0);     pc = __builtin_fma(pc, x, 1.0 / 39916800.0);
+    pa = __builtin_fma(pa, x, 1.0 / 5040.0);       pb = __builtin_fma(pb, x, 1.0 / 40320.0);       pc = __builtin_fma(pc, x, 1.0 / 362880.0);
+    pa = __builtin_fma(pa, x, 1.0 / 120.0);        pb = __builtin_fma(pb, x, 1.0 / 720.0);         pc = __builtin_fma(pc, x, 1.0 / 5040.0);
+    pa = __builtin_fma(pa, x, 1.0 / 6.0);          pb = __builtin_fma(pb, x, 1.0 / 24.0);          pc = __builtin_fma(pc, x, 1.0 / 120.0);
+    a = __builtin_fma(pa, x, 1.0);
+    b = __builtin_fma(pb, x, 0.5);
+    c = __builtin_fma(pc, x, 1.0 / 6.0);
   }
 }
 
@@ -67,9 +80,26 @@ MAVBA_HD void cam_prepare(const double* pose, double* rec) {
 
 // 1 / x and 1 / sqrt(x) per observation (round 5). The IEEE division and sqrt + division of the device build are 20-35
 // FP64 instructions each on a pipe that every per-observation kernel is bound by; the hardware seeds (v_rcp_f64 / v_rsq_f64,
-// ~2^-24 relative) with two Newton steps / one third-order step are 5-6 and end within 1-2 ulp (measured for the rsqrt:
-// 1.4e-16 against 1.1e-16 correctly rounded, scripts/_dbg/tile_bench.hip). Host builds (tests, the fixed-cost blocks) keep
-// the IEEE forms: the two agree to ~2e-16, far inside every tolerance of the parity tests.
+// ~2^-24 relative) with two Newton steps / one third-order step are 5-6. Host builds (tests, the fixed-cost blocks) keep the
+// IEEE forms.
+//
+// Accuracy of the device build, claimed and held by tests/test_gpu_obs_math.py against a 60-digit reference
+// (tests/golden/obs_math_hp.npz, ~4 000 arguments each: log-uniform, every few powers of two with their neighbours, the
+// mantissas 1 + 2^-52 and 2 - 2^-52; errors in ulps of the correctly rounded result, measured on an MI355X):
+//   rcp_obs    claim <= 2 ulp   measured 0.500 ulp   1e-150 <= |x| <= 1e150 (every result was the correctly rounded one)
+//   rsqrt_obs  claim <= 2 ulp   measured 0.963 ulp   1e-150 <= x <= 1e300   (host 1 / sqrt(x): 1.381 ulp)
+//   log_obs    claim <= 2 ulp   measured 1.775 ulp   1 <= x <= 1e300, 1 + 10^u for u in [-16, 0] and both sides of the
+//                                                    fold at sqrt(2) included; log_obs(1) = 0 exactly
+// Outside those ranges (no ulp bar; the rule is: within the bar of the exact value or not finite, never a finite wrong value):
+//   x               rcp_obs host / device    rsqrt_obs host / device    log_obs host / device
+//   +0, -0          +inf, -inf / nan         +inf, -inf / nan           -inf / nan
+//   5e-324, 1e-310  +inf / nan               finite / finite (ok)       finite / finite (ok)
+//   1e-300, 1e300   finite / finite (ok)     finite / finite (ok)       finite / finite (ok)
+//   +inf (-inf)     0 / nan                  0 (nan) / nan              +inf (nan) / nan
+//   nan             nan / nan                nan / nan                  nan / nan
+//   x < 0           as |x|, sign kept        nan / nan                  nan / nan
+// (rcp_obs: the Newton residual of an infinite seed is inf * 0. log_obs answered log(0) = -5.05 and finite values for some
+// negative arguments until the test above saw it; the select in log_obs is for them.)
 MAVBA_HD double rcp_obs(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   double y = __builtin_amdgcn_rcp(x);
@@ -94,8 +124,8 @@ MAVBA_HD double rsqrt_obs(double x) {
 // log(x) per observation, x >= 1 and finite (the Cauchy loss: x = 1 + s / b), round 6. The library's log is ~90 vector
 // instructions per observation in every kernel that needs the cost (it carries a double-double tail for < 1 ulp); this one
 // is 35: x = 2^e m with m in [sqrt(1/2), sqrt(2)), t = (m - 1) / (m + 1) <= 0.1716, log m = 2 t (1 + t^2/3 + ... + t^20/21)
-// (the tail is below 7e-19 of the leading term), e ln 2 in two parts. Error <= 2 ulp (tests/test_host_math.py compares
-// the same arithmetic on the host with log over 1 <= x < 1e12); host builds keep the library's.
+// (the tail is below 7e-19 of the leading term), e ln 2 in two parts. Error <= 2 ulp on the device (table above;
+// tests/test_host_math.py compares the same arithmetic on the host with log over 1 <= x < 1e12); host builds keep the library's.
 // (the series, given x = 2^e m with m in [0.5, 1): host-callable for the test)
 MAVBA_HD double log_from_parts(double m, int e) {
   const bool low = m < 0.70710678118654752440;
@@ -118,7 +148,8 @@ MAVBA_HD double log_from_parts(double m, int e) {
 }
 MAVBA_HD double log_obs(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  return log_from_parts(__builtin_amdgcn_frexp_mant(x), __builtin_amdgcn_frexp_exp(x));
+  const double l = log_from_parts(__builtin_amdgcn_frexp_mant(x), __builtin_amdgcn_frexp_exp(x));
+  return x > 0.0 ? l : __builtin_nan("");  // the parts of a zero or a negative x make a finite value
 #else
   return log(x);
 #endif
@@ -327,9 +358,14 @@ MAVBA_HD void obs_backsub_term(int model, const double* rec, const double* cam, 
 // Cauchy robustifier on s = |r|^2: returns the row weight sqrt(rho') and the
 // block cost rho/2. inv_b = 1/a^2, b = a^2.
 MAVBA_HD void cauchy_weight(double s, double b, double inv_b, double& w, double& half_rho) {
-  const double sum = 1.0 + s * inv_b;
-  half_rho = 0.5 * b * log_obs(sum);
+  // log(1 + x) from the rounded sum: 1 + x keeps an absolute error of 1e-16, which is all of log(1 + x) ~ x for a small
+  // residual (x = 1e-4 lost four digits of the cost term). x - (sum - 1) is that rounding error exactly, and d log = it / sum,
+  // with 1 / sum = w^2 already at hand. (An infinite s keeps its infinite cost: inf - inf would make it NaN.)
+  const double x = s * inv_b;
+  const double sum = 1.0 + x;
   w = rsqrt_obs(sum);
+  const double l = log_obs(sum);
+  half_rho = 0.5 * b * (sum < 1e300 ? __builtin_fma(x - (sum - 1.0), w * w, l) : l);
 }
 
 // ---------------------------------------------------------------------------
@@ -445,6 +481,39 @@ MAVBA_HD void git_mul(const double* Gi, const double* x, double* y) {
 }
 
 MAVBA_HD double clampd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// ---------------------------------------------------------------------------
+// Test entry (mavba_debug_obs_math): one case of one of the functions above, by whichever build compiles this - the
+// host loop of api.hip and the one-thread-per-case kernel of kernels.hip call this same body, so the test compares
+// the two builds of the functions themselves. Doubles in / out per case by kind:
+//   0 rcp_obs       x                                     -> 1
+//   1 rsqrt_obs     x                                     -> 1
+//   2 log_obs       x                                     -> 1
+//   3 rot_coeffs    th2                                   -> a, b, c
+//   4 cauchy_weight s, b (inv_b = 1 / b as session.h)     -> w, half_rho
+//   5 obs_jacobian  model, pose[6], cam[9], X[3], uv[2]   -> r[2], Jc[12], Jp[6], Jk[18]
+//   6 obs_residual  as 5                                  -> r[2]
+//   7 obs_backsub_term  as 5, then dc[6], dk[9]           -> r[2], t[3]
+// ---------------------------------------------------------------------------
+#define MAVBA_OBS_MATH_KINDS 8
+MAVBA_HD int obs_math_in_width(int kind) { return kind <= 3 ? 1 : kind == 4 ? 2 : kind <= 6 ? 21 : 36; }
+MAVBA_HD int obs_math_out_width(int kind) {
+  return kind <= 2 ? 1 : kind == 3 ? 3 : kind == 4 ? 2 : kind == 5 ? 38 : kind == 6 ? 2 : 5;
+}
+MAVBA_HD void obs_math_case(int kind, const double* q, double* o) {
+  if (kind == 0) { o[0] = rcp_obs(q[0]); return; }
+  if (kind == 1) { o[0] = rsqrt_obs(q[0]); return; }
+  if (kind == 2) { o[0] = log_obs(q[0]); return; }
+  if (kind == 3) { rot_coeffs(q[0], o[0], o[1], o[2]); return; }
+  if (kind == 4) { cauchy_weight(q[0], q[1], 1.0 / q[1], o[0], o[1]); return; }
+  const int model = (int)q[0];
+  const double *pose = q + 1, *cam = q + 7, *X = q + 16, *uv = q + 19;
+  double rec[9];
+  cam_prepare(pose, rec);
+  if (kind == 5) obs_jacobian(model, rec, cam, X, uv[0], uv[1], o, o + 2, o + 14, o + 20);
+  else if (kind == 6) obs_residual(model, rec, cam, X, uv[0], uv[1], o);
+  else obs_backsub_term(model, rec, cam, X, uv[0], uv[1], q + 21, q + 27, o, o + 2);
+}
 
 // Packed index of (r, c), r <= c, in the upper triangle of an n x n symmetric
 // matrix stored row by row: (0,0),(0,1)...(0,n-1),(1,1)...

@@ -340,6 +340,7 @@ void launch_reduce_tasks(hipStream_t st, const ReduceTasks& tasks, int n, const 
 constexpr int kLmPubDoubles = SC_COUNT + 8;  // scalars | code radius decrease_factor rel step_norm cost_change - | seq
 void launch_lm_snapshot(hipStream_t st, const LmSpec& spec, double* dec, double* host_pub, double seq, double* fail_slots /* SC_FAIL, SC_FAIL_FRONT: cleared behind the read */);
 void launch_lm_decide_cases(hipStream_t st, int n, const double* in, double* out);  // test entry
+void launch_obs_math_cases(hipStream_t st, int kind, int n, const double* in, double* out);  // test entry
 // k_reduce_tasks + k_lm_snapshot in one work-group (the n reductions one after the other, then the decision)
 void launch_lm_tail(hipStream_t st, const ReduceTasks& tasks, int n, const LmSpec& spec, double* dec, double* host_pub, double seq, double* fail_slots);
 // The tail of an evaluation: per-image sums (k_camera_reduce_img), per-camera sums (k_camera_reduce_cam), norms

@@ -2119,6 +2119,20 @@ __global__ void k_lm_decide_cases(int n, const double* __restrict__ in, double* 
 void launch_lm_decide_cases(hipStream_t st, int n, const double* in, double* out) {
   if (n > 0) hipLaunchKernelGGL(k_lm_decide_cases, dim3((n + 255) / 256), dim3(256), 0, st, n, in, out);
 }
+// Test entry (mavba_debug_obs_math): `n` cases of one per-observation function of ba_math.h by the device build, one thread
+// per case (obs_math_case lists the kinds and the widths of a case's input and output).
+__global__ void k_obs_math_cases(int kind, int n, const double* __restrict__ in, double* __restrict__ out) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  double q[36], o[38];
+  const int wi = obs_math_in_width(kind), wo = obs_math_out_width(kind);
+  for (int i = 0; i < wi; ++i) q[i] = in[(size_t)c * wi + i];
+  obs_math_case(kind, q, o);
+  for (int i = 0; i < wo; ++i) out[(size_t)c * wo + i] = o[i];
+}
+void launch_obs_math_cases(hipStream_t st, int kind, int n, const double* in, double* out) {
+  if (n > 0) hipLaunchKernelGGL(k_obs_math_cases, dim3((n + 63) / 64), dim3(64), 0, st, kind, n, in, out);
+}
 void launch_lm_snapshot(hipStream_t st, const LmSpec& spec, double* dec, double* host_pub, double seq, double* fail_slots) {
   hipLaunchKernelGGL(k_lm_snapshot, dim3(1), dim3(64), 0, st, spec, dec, host_pub, seq, fail_slots);
 }

@@ -30,6 +30,11 @@ int hm_chol3_inv(const double* C, double* Gi) { return mavba::chol3_inv(C, Gi) ?
 void hm_cauchy(double s, double a, double* w, double* half_rho) {
   mavba::cauchy_weight(s, a * a, 1.0 / (a * a), *w, *half_rho);
 }
+// n cases of one function by kind: the body of mavba_debug_obs_math (ba_math.h, obs_math_case) as the host builds it
+void hm_obs_math(int kind, int n, const double* in, double* out) {
+  const int wi = mavba::obs_math_in_width(kind), wo = mavba::obs_math_out_width(kind);
+  for (int c = 0; c < n; ++c) mavba::obs_math_case(kind, in + (long)c * wi, out + (long)c * wo);
+}
 // the device build's log series (log_obs) on the host: frexp supplies the parts the hardware instructions give the kernel
 double hm_log_series(double x) { int e; const double m = std::frexp(x, &e); return mavba::log_from_parts(m, e); }
 }
